@@ -1,6 +1,7 @@
 """Benchmark: sample-pairs/s of the whole pairwise-distance path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full]
+                    [--dump-outputs DIR]
 
 One step = one pass of the hot path over the whole synthetic batch with the
 inputs already resident in HBM: 2-bit pack -> seed index build -> seed-and-
@@ -11,8 +12,13 @@ the sample pairs are sharded by sequence length (rc_plan_shards), every rank
 aligns its pairs and runs reciprocal best hits for them, the graph edges are
 exchanged with one RCCL all-gather, and every rank finishes the graph.
 
-Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the roofline
-model and the CPU baseline.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line
+(rank 0). --full adds the legs that take runs of their own: the CPU baseline
+(the CPU port on this host's cores, before the GPU is touched) and the
+wall-clock leg (FASTA files -> rna_clique() -> matrix.h5); their fields are
+null in a plain run's line. --dump-outputs DIR writes what the last timed step
+returned (the distance matrix) as DIR/distance.npy. See DESIGN.md §Measurement
+for the roofline model and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -32,13 +38,17 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md)
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and the wall-clock leg (each a run of its own)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (the distance matrix, float64) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the wall-clock leg (FASTA files -> rna_clique() -> matrix.h5)")
+                    help="with --full: skip the wall-clock leg (FASTA files -> rna_clique() -> matrix.h5)")
     ap.add_argument("--cpu-pairs", type=int, default=0,
                     help="sample pairs the CPU baseline times (2 directed searches each; "
                          "default 2 x the worker count)")
@@ -48,7 +58,10 @@ def parse_args():
                     help="emulate rank R of an S-GPU run on this one GPU: only that rank's samples are "
                          "generated and resident, its pairs aligned (align + RBH timed); prints a "
                          "shard_emulation line (C5 on a 1-GPU box)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -283,6 +296,16 @@ def e2e_wall_clock(samples, genes, rank, world, dist, ref):
                     "tables + graph.pkl + matrix.h5 (every output the reference writes)"}
 
 
+def dump_outputs(out_dir, mat):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step, one float64 .npy per array. The distance matrix (N x N, rows and
+    columns in sorted label order) is all of it; the inputs are seeded, so two
+    builds run with the same arguments can be compared entry for entry."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "distance.npy"), np.ascontiguousarray(mat, dtype=np.float64))
+
+
 def shard_samples(config, shard_count, rank):
     """(samples, needed sample set, pair plan) of rank `rank` of a
     `shard_count`-GPU run of `config`: with the config's per-node random
@@ -396,7 +419,7 @@ def main():
     n = len(samples)
     pairs = n * (n - 1) // 2
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU port on this host's cores, before anything touches the GPU
         # (the device count below included: the pool's workers are forked)
         workers, why = cpu_workers(samples, args.cpu_workers)
@@ -452,10 +475,12 @@ def main():
         dt = float(t.item())
     ms_per_step = 1e3 * dt / args.steps
     value = pairs * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mat)
     st = eng.stats()
     tm = eng.timings()
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         eng.close()   # free this engine's HBM before rna_clique() builds its own
         e2e = e2e_wall_clock(samples, cfg["genes"], rank, world, dist, (labels, mat))
     if rank != 0:

@@ -9,8 +9,8 @@
 #   tests            every -m gpu test, one process
 #   tests:EXPR       -m gpu tests matching -k EXPR
 #   bench[:CFG]      bench.py --config CFG (default C3), 3 steps, no CPU baseline, no e2e
-#   benchfull        bench.py with its defaults (CPU baseline + wall-clock leg)
-#   e2e[:CFG]        bench.py with the wall-clock leg, no CPU baseline
+#   benchfull        bench.py --full (CPU baseline + wall-clock leg)
+#   e2e[:CFG]        bench.py --full with the wall-clock leg, no CPU baseline
 #   stats[:CFG]      rocprofv3 --kernel-trace --stats of bench.py --config CFG
 #   pmc[:CFG]        the PMC passes of scripts/gpu_pmc.sh (same-source counters)
 #   pmcx:CFG:G1;G2   PMC passes with the given counter groups (';' between passes,
@@ -51,8 +51,8 @@ for step in "$@"; do
            fi ;;
     env) export "$a"; ET="${ET}_${a//\//_}"; log "export $a" ;;
     bench) c=${a:-C3}; run 600 "$D/${c}_bench${ET}.json" python bench.py --config "$c" --steps 3 --warmup 1 --no-cpu-baseline --no-e2e || exit $? ;;
-    benchfull) run 900 "$D/bench_default.json" python bench.py || exit $? ;;
-    e2e) c=${a:-C3}; run 600 "$D/${c}_e2e.json" python bench.py --config "$c" --steps 3 --warmup 1 --no-cpu-baseline || exit $? ;;
+    benchfull) run 900 "$D/bench_default.json" python bench.py --full || exit $? ;;
+    e2e) c=${a:-C3}; run 600 "$D/${c}_e2e.json" python bench.py --full --config "$c" --steps 3 --warmup 1 --no-cpu-baseline || exit $? ;;
     stats) c=${a:-C3}
            run 600 "$D/${c}_stats${ET}.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$D/${c}_stats${ET}" -o run -- python3 bench.py --config "$c" --steps 3 --warmup 1 --no-cpu-baseline --no-e2e || exit $? ;;
     pmc) c=${a:-C3}; log "bash scripts/gpu_pmc.sh $c  (-> gpurun_out/pmc_$c)"; bash scripts/gpu_pmc.sh "$c" || exit $? ;;

@@ -1,6 +1,7 @@
-"""bench.py's roofline pieces that need no GPU: the committed PMC summary of
-the current sources is found by its source hash, and the extension's issue
-roofline is priced against the row kernel's own time."""
+"""bench.py's pieces that need no GPU: the committed PMC summary of the
+current sources is found by its source hash, the extension's issue roofline
+is priced against the row kernel's own time, a plain run leaves out what
+--full adds, and --dump-outputs writes float64 .npy files."""
 import json
 import os
 import sys
@@ -34,6 +35,30 @@ def test_issue_roofline_uses_the_row_kernel_time():
     del iss["kernel_ms"]
     r = bench.issue_roofline(iss, 92.0)
     assert r["kernel_ms"] == 92.0 and "live" in r["kernel_ms_source"]
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """The CPU baseline and the wall-clock leg run only with --full; --steps
+    is the number of timed steps, so it cannot be 0."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = bench.parse_args()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 2, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+def test_dump_outputs_writes_the_matrix_as_float64(tmp_path):
+    import numpy as np
+    mat = np.array([[0.0, 0.25], [0.25, 0.0]])
+    out = tmp_path / "sub" / "dump"
+    bench.dump_outputs(str(out), mat)
+    assert sorted(os.listdir(out)) == ["distance.npy"]
+    got = np.load(out / "distance.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, mat)
 
 
 def test_committed_summary_has_the_row_kernel_time():
