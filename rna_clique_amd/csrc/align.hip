@@ -1450,11 +1450,11 @@ __global__ __launch_bounds__(EBLOCK, EXT_MIN_WAVES) void extend_kernel(Db db, Ex
         }
     }
     if (lane == 0 && P.counters) {
-        atomicAdd(&P.counters[0], (unsigned long long)steps);
-        atomicAdd(&P.counters[1], (unsigned long long)exts);
-        atomicAdd(&P.counters[2], (unsigned long long)ncands);
-        if (edges) atomicAdd(&P.counters[7], (unsigned long long)edges);     // extensions the band bound
-        if (capped) atomicAdd(&P.counters[10], (unsigned long long)capped);  // candidates MAX_HSP bound
+        atomicAdd(&P.counters[DC_STEPS - DC_COUNTERS], (unsigned long long)steps);
+        atomicAdd(&P.counters[DC_EXTS - DC_COUNTERS], (unsigned long long)exts);
+        atomicAdd(&P.counters[DC_CANDS - DC_COUNTERS], (unsigned long long)ncands);
+        if (edges) atomicAdd(&P.counters[DC_BAND_BOUND - DC_COUNTERS], (unsigned long long)edges);
+        if (capped) atomicAdd(&P.counters[DC_MAXHSP - DC_COUNTERS], (unsigned long long)capped);
     }
 }
 
@@ -2595,24 +2595,24 @@ __global__ __launch_bounds__(EBLOCK, MINW) void extend_rows_kernel(RowArgs)
 #ifdef RC_ROW_TIMING
     unsigned long long *const counters = row_args()->P.counters;
     if (lane == 0 && counters) {
-        atomicAdd(&counters[8], t_tr);
-        atomicAdd(&counters[9], t_st);
-        atomicAdd(&counters[27], t_fe);   // (d_count[28], [29]: slots nothing else uses)
-        atomicAdd(&counters[28], t_sl);
-        atomicAdd(&counters[29], t_ei);
+        atomicAdd(&counters[DC_T_TRANS - DC_COUNTERS], t_tr);
+        atomicAdd(&counters[DC_T_STEPS - DC_COUNTERS], t_st);
+        atomicAdd(&counters[DC_T_FETCH - DC_COUNTERS], t_fe);   // (the DC_T_* slots past the view: nothing else uses them)
+        atomicAdd(&counters[DC_T_SLIDE - DC_COUNTERS], t_sl);
+        atomicAdd(&counters[DC_T_START - DC_COUNTERS], t_ei);
     }
     if (rl == 0 && had && !ov16) c16++;
     if (rl == 0 && counters) {
-        atomicAdd(&counters[26], n16);
-        atomicAdd(&counters[30], c16);
-        atomicAdd(&counters[31], sl16);
+        atomicAdd(&counters[DC_T_N16 - DC_COUNTERS], n16);
+        atomicAdd(&counters[DC_T_C16 - DC_COUNTERS], c16);
+        atomicAdd(&counters[DC_T_SL16 - DC_COUNTERS], sl16);
     }
 #endif
     unsigned long long *const ctr = row_args()->P.counters;
     if (rl == 0 && d6) atomicAdd(&rcnt[5], (uint32_t)d6);   // the last extension's steps
     __syncthreads();
-    if (threadIdx.x < 4 && ctr) atomicAdd(&ctr[1 + threadIdx.x], (unsigned long long)rcnt[threadIdx.x]);   // [4]: slides
-    if (threadIdx.x == 5 && ctr) atomicAdd(&ctr[0], (unsigned long long)(rcnt[5] / 6u));
+    if (threadIdx.x < 4 && ctr) atomicAdd(&ctr[DC_EXTS - DC_COUNTERS + threadIdx.x], (unsigned long long)rcnt[threadIdx.x]);   // ... DC_SLIDES
+    if (threadIdx.x == 5 && ctr) atomicAdd(&ctr[DC_STEPS - DC_COUNTERS], (unsigned long long)(rcnt[5] / 6u));
 }
 
 // The candidates' first-seed extensions -> box; the other seeds of the
@@ -2766,7 +2766,7 @@ __device__ __forceinline__ void later_full(const LaterParams &L, int dir, uint64
 {
     const unsigned long long i = atomicAdd(&L.full_n[dir], 1ull);
     (dir ? L.full1 : L.full0)[i] = (uint32_t)ci;
-    if (L.counters) atomicAdd(&L.counters[1], 1ull);
+    if (L.counters) atomicAdd(&L.counters[LC_WHOLE], 1ull);
 }
 
 // One round of the later-seed rounds, one thread per active search: take the
@@ -2993,7 +2993,7 @@ __global__ __launch_bounds__(256) void later_finish_kernel(ExtParams P, LaterPar
         wb = (unsigned long long)__shfl((long long)wb, 63);
         if (P.counters) {
             const uint64_t cm = __ballot(capped);
-            if (lane == 0 && cm) atomicAdd(&P.counters[10], (unsigned long long)__popcll(cm));
+            if (lane == 0 && cm) atomicAdd(&P.counters[DC_MAXHSP - DC_COUNTERS], (unsigned long long)__popcll(cm));
         }
         if (!live) continue;
         const uint32_t obase = need ? (uint32_t)(wb + incl - need) : 0u;
@@ -3318,11 +3318,6 @@ int row_slot_words_max(bool amb)
     return (int)((per_block - fixed) / ((size_t)rows * na * 8));
 }
 
-// Row kernel (first seeds) over all candidates, first_finish_kernel, then
-// extend_kernel over the candidates either deferred (sub-band overflow,
-// seeds outside the first box; without the windowed kernel transcripts
-// longer than the row staging slot). The deferred count stays on the device:
-// the list launch reads it.
 // extend_kernel over the searches the row kernels left (B.defer, and for
 // shared searches the reverse ones, B.defer_r)
 static void extend_lists(bool amb, const Db &db, const ExtParams &B, hipStream_t st)
@@ -3344,19 +3339,20 @@ static void extend_lists(bool amb, const Db &db, const ExtParams &B, hipStream_t
     }
 }
 
-// The extend_kernel launches of launch_extend_rows alone: after it ran with
-// lists = false, or again after the HSP overflow buffer overflowed (only
-// extend_kernel writes it; the row kernels' results, first_finish_kernel's
-// and the defer lists stand)
-void launch_extend_retry(bool amb, const Db &db, const ExtParams &P, hipStream_t st)
+// The extend_kernel launches over the searches launch_extend_rows deferred
+// (sub-band overflow, seeds outside the first box; without the windowed
+// kernel transcripts longer than the row staging slot): after it, or again
+// after the HSP overflow buffer overflowed (only extend_kernel writes it; the
+// row kernels' results, first_finish_kernel's and the defer lists stand).
+// The deferred counts stay on the device: the list launches read them.
+void launch_extend_retry(bool amb, const Db &db, const ExtParams &P, const RowOpts &O, hipStream_t st)
 {
     if (P.n_cand == 0) return;
     ExtParams W = P;
     W.list = nullptr;
     W.list_n = nullptr;
     W.resume = nullptr;
-    const char *r64 = getenv("RC_ROW64");
-    if (!P.share && r64 && atoi(r64)) {
+    if (!P.share && O.row64) {
         W.defer = P.defer2;
         W.defer_count = P.defer2_count;
     }
@@ -3364,24 +3360,22 @@ void launch_extend_retry(bool amb, const Db &db, const ExtParams &P, hipStream_t
 }
 
 // Later-seed rounds over the searches first_finish_kernel deferred (shared
-// searches; after launch_extend_rows with lists = false): MAX_HSP rounds of
+// searches; after launch_extend_rows): MAX_HSP rounds of
 // later_round_kernel, with the row kernels (32-lane, then the 64-lane pass
 // over what outgrew the sliding sub-band) over each round's seeds between
 // them. Every count stays on the device: an empty round is a few idle
 // launches. cnt: LATER_CNT zeroed counters per round; the work buffers
 // (vc, list, box) and the active lists alternate between rounds.
-void launch_later_rounds(bool amb, const Db &db, const ExtParams &P, const LaterParams &L0, Cand *const vc[2],
-                         uint32_t *const list[2], int32_t *const box[2], uint32_t *const act[2],
+void launch_later_rounds(bool amb, const Db &db, const ExtParams &P, const RowOpts &O, const LaterParams &L0,
+                         Cand *const vc[2], uint32_t *const list[2], int32_t *const box[2], uint32_t *const act[2],
                          unsigned long long *cnt, hipStream_t st)
 {
     if (!L0.n_search) return;
-    const char *wv = getenv("RC_WIDE");
-    const bool widep = !(wv && atoi(wv) == 0) && P.wide0;
+    const bool widep = O.wide && P.wide0;
     // later seeds nearly all outgrow the 32-lane window (C3v: 15.3 M of 15.3 M,
     // profiles/r06_later): straight to 64-lane rows (RC_LATER_ROWS=32: the
     // 32-lane pass first)
-    const char *rv = getenv("RC_LATER_ROWS");
-    const bool rows64 = !(rv && atoi(rv) == 32);
+    const bool rows64 = O.later_rows != 32;
     uint64_t g = (L0.n_search + 255) / 256;
     if (g > 8192) g = 8192;
     for (int r = 0; r < MAX_HSP; r++) {
@@ -3440,21 +3434,18 @@ void launch_later_finish(const ExtParams &P, const LaterParams &L, hipStream_t s
     hipLaunchKernelGGL(later_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, P, L);
 }
 
-// lists = false: up to first_finish_kernel only (the caller sizes the HSP
-// overflow buffer from the defer counts, then launch_extend_retry)
-void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, int row_width, hipStream_t st, bool lists)
+// Row kernels (first seeds) over all candidates, then first_finish_kernel
+// (the caller sizes the HSP overflow buffer from the defer counts, then
+// launch_extend_retry)
+void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, const RowOpts &O, hipStream_t st)
 {
     if (P.n_cand == 0) return;
-    (void)row_width;
     ExtParams W = P;
     W.list = nullptr;
     W.list_n = nullptr;
     // saved extension states: only the shared-search 32-lane passes write
     // them and only their 64-lane passes read them
     W.resume = nullptr;
-    auto extend_lists = [&](const ExtParams &B) {
-        if (lists) rcg::extend_lists(amb, db, B, st);
-    };
     uint64_t g = (P.n_cand + 255) / 256;
     if (g > 65536) g = 65536;
     if (P.share) {
@@ -3467,8 +3458,7 @@ void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, int row_widt
         // them also have seeds outside the first box; extend_kernel starts
         // those searches from the first seed's HSP (P.reuse_first), so the
         // 64-lane pass is not redone: C3v 806 vs 875 ms per step.
-        const char *wv = getenv("RC_WIDE");
-        const bool widep = !(wv && atoi(wv) == 0) && P.wide0;
+        const bool widep = O.wide && P.wide0;
         auto wide_pass = [&](const ExtParams &B, uint32_t *lst, unsigned long long *lst_n, unsigned long long *wk) {
             ExtParams V = B;
             V.list = lst;
@@ -3499,7 +3489,6 @@ void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, int row_widt
         W.list = nullptr;
         W.list_n = nullptr;
         hipLaunchKernelGGL(first_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, W);
-        extend_lists(W);
         return;
     }
     // independent searches / spec 5b: 32-lane rows over every candidate
@@ -3508,10 +3497,8 @@ void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, int row_widt
     // because 40 % of what it finishes still has seeds outside the first box
     // and is redone whole by the one-wave kernel): the candidates whose
     // frontier left the sub-band, on 64-lane rows (the spec's whole band)
-    const char *r64 = getenv("RC_ROW64");
-    if (!(r64 && atoi(r64))) {
+    if (!O.row64) {
         hipLaunchKernelGGL(first_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, W);
-        extend_lists(W);
         return;
     }
     ExtParams W2 = W;
@@ -3525,7 +3512,6 @@ void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, int row_widt
     W3.defer = P.defer2;
     W3.defer_count = P.defer2_count;
     hipLaunchKernelGGL(first_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, W3);
-    extend_lists(W3);
 }
 
 void launch_group(const GroupParams &P, int pass, hipStream_t st)

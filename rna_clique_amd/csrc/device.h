@@ -255,6 +255,51 @@ struct SeedParams {
     uint8_t *big_segT;            // big_cap per workgroup
 };
 
+// Slots of the per-tile counter block (the engine's d_count, one unsigned long
+// long each). The kernels see [DC_COUNTERS, DC_COUNTERS_END) as
+// ExtParams::counters, so counters[SLOT - DC_COUNTERS] is d_count[SLOT] (the
+// RC_ROW_TIMING builds index the DC_T_* slots through the same view).
+enum DCount {
+    DC_OVF = 0,         // ExtParams::ovf_count: HSPs appended to the overflow buffer
+    DC_COUNTERS = 1,    // base of the ExtParams::counters view
+    DC_STEPS = 1,       // greedy steps
+    DC_EXTS,            // extensions
+    DC_CANDS,           // candidates
+    DC_FULLBAND,        // candidates that outgrew the 32-lane window
+    DC_SLIDES,          // window slides
+    DC_DEFER,           // ExtParams::defer_count (the same slot as counters[5])
+    DC_WORK,            // ExtParams::work (the same slot as counters[6])
+    DC_BAND_BOUND,      // extensions the band bound
+    DC_T_TRANS,         // RC_ROW_TIMING: wave cycles in transitions
+    DC_T_STEPS,         // RC_ROW_TIMING: wave cycles in steps
+    DC_MAXHSP,          // candidates MAX_HSP bound
+    DC_COUNTERS_END,    // one past the view the host reads back
+    DC_BIG = DC_COUNTERS_END,   // SeedParams::big_n
+    DC_BIG_RETRY,       // SeedParams::big_retry_n (follows DC_BIG: cleared together)
+    DC_DEFER2,          // ExtParams::defer2_count
+    DC_WORK2,           // ExtParams::work2
+    DC_LIST2,           // list2_n: the seed kernel counts, the extension reads
+    DC_DEFER_R,         // ExtParams::defer_r_count
+    DC_WORK3,           // ExtParams::work3
+    DC_MBIG,            // GroupParams::mbig_n
+    DC_WIDE0,           // ExtParams::wide0_n
+    DC_WIDE1,           // ExtParams::wide1_n
+    DC_WORK_W0,         // ExtParams::work_w0
+    DC_WORK_W1,         // ExtParams::work_w1
+    DC_WHY,             // ExtParams::why[3]
+    DC_WHY_END = DC_WHY + 3,
+    // RC_ROW_TIMING builds only; the host clears them after printing
+    DC_T_N16 = DC_WHY_END,   // row steps before a live span over 14 diagonals
+    DC_T_FETCH,         // wave cycles in fetches
+    DC_T_SLIDE,         // ... in window slides
+    DC_T_START,         // ... in extension starts
+    DC_T_C16,           // candidates never over 14 diagonals
+    DC_T_SL16,          // 16-lane window slides
+    DC_N = 34           // the block's size
+};
+static_assert(DC_DEFER == DC_COUNTERS + 5 && DC_WORK == DC_COUNTERS + 6, "defer_count and work alias counters[5], [6]");
+static_assert(DC_COUNTERS_END == 12 && DC_WHY == 24 && DC_T_SL16 == 32 && DC_T_SL16 < DC_N, "d_count layout");
+
 // extend_kernel: one wave per candidate, greedy X-drop, purge, e-value cut.
 struct ExtParams {
     int32_t xdrop;
@@ -274,14 +319,17 @@ struct ExtParams {
     uint64_t ovf_cap;
     unsigned long long *ovf_count;
     unsigned int *status;         // bit 0 overflow
-    unsigned long long *counters; // [0] greedy steps, [1] extensions, [2] candidates (one atomic per wave),
-                                  // [4] full-band recomputations
+    unsigned long long *counters; // d_count + DC_COUNTERS: counters[DC_x - DC_COUNTERS] (one atomic per wave);
+                                  // null: a retry, whose work the first attempt counted
     // row kernels: staging slot (u64 words per sequence); win: the slot is
     // shorter than the longest transcript, the windowed instantiation runs
     int32_t dsw;
     int32_t win;
     int32_t *cand_box;            // row kernel: status + right/left results of each candidate's first seed
     int32_t chunk;                // row kernel: candidates per work grab (0: static round robin)
+    // (first pass: work and defer_count are d_count[DC_WORK] and [DC_DEFER],
+    // which are also counters[6] and counters[5] -- the host reads the
+    // deferred count from there; list passes point them elsewhere)
     unsigned long long *work;     // row kernel: work counter
     uint32_t *defer;
     unsigned long long *defer_count;
@@ -343,6 +391,9 @@ constexpr int LATER_ACTIVE = -1, LATER_FULL = -2;
 // device counters per round: work items, searches still active, the 32-lane
 // pass's work counter, its wide list, the 64-lane pass's work counter
 constexpr int LATER_CNT = 8;
+// after the rounds' counters, LaterParams::counters: [0] unused, searches run
+// whole, then full_n[2]
+enum { LC_WHOLE = 1, LC_FULL_N = 2, LC_N = 4 };
 struct LaterParams {
     int32_t *state;                       // [n_cap][LATER_REC]
     uint64_t n_search, n0;                // searches; the first n0 are forward ones (defer0), then defer1
@@ -360,7 +411,7 @@ struct LaterParams {
     uint32_t *act_out;
     unsigned long long *act_out_n;
     unsigned long long *work_n;           // work items of the round
-    unsigned long long *counters;         // [0] (unused), [1] searches run whole
+    unsigned long long *counters;         // [LC_WHOLE] searches run whole
 };   // phase, kof, d6, best, best record (i, gap, d6, diagonal), right results, R[32], goe[32]
 
 // DHsp.strand carries, besides the strand (bit 0), the direction flags of a
@@ -370,6 +421,14 @@ constexpr int HSP_FWD = 2, HSP_REV = 4, HSP_IDX_SHIFT = 3;
 
 // cand_box record: BOX_REC ints per candidate (align.hip FX_*)
 constexpr int BOX_REC = 12;
+
+// Host side only (never passed to a kernel): which row passes the extension
+// launchers of align.hip queue, from the engine's knobs
+struct RowOpts {
+    bool wide;        // RC_WIDE: a 64-lane pass after each 32-lane pass (shared searches)
+    bool row64;       // RC_ROW64: a 64-lane pass over the 32-lane pass's deferrals (independent searches)
+    int later_rows;   // RC_LATER_ROWS: 32 = the later-seed rounds run the 32-lane pass first
+};
 
 
 // group kernels: candidates of each (gene, sample) -> contiguous HSP groups.

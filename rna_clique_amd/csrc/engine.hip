@@ -50,7 +50,6 @@ bool os_sort_keys(uint64_t *keys, uint64_t *alt, uint64_t n, int bb, uint32_t *s
                   uint32_t &epoch, hipStream_t st, const std::function<void()> &after_prep, bool counted,
                   const TxInfo *gen_tx, const uint64_t *gen_koff, const uint64_t *gen_F, uint32_t gen_ntx,
                   uint32_t *gen_tile);
-uint64_t os_gen_tile_words(uint64_t n);
 void os_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
                   uint64_t n, uint32_t *scratch, hipStream_t st);
 void launch_tx_masked(const TxInfo *, uint32_t, const uint64_t *, uint8_t *, hipStream_t);
@@ -72,10 +71,10 @@ void launch_dust(bool, uint64_t, uint64_t, const uint64_t *, const uint64_t *, c
 uint32_t dust_scratch_words(uint32_t);
 uint64_t dust_event_words(uint32_t);
 void launch_extend(bool, const Db &, const ExtParams &, hipStream_t);
-void launch_extend_rows(bool, const Db &, const ExtParams &, int, hipStream_t, bool);
-void launch_extend_retry(bool, const Db &, const ExtParams &, hipStream_t);
-void launch_later_rounds(bool, const Db &, const ExtParams &, const LaterParams &, Cand *const[2], uint32_t *const[2],
-                         int32_t *const[2], uint32_t *const[2], unsigned long long *, hipStream_t);
+void launch_extend_rows(bool, const Db &, const ExtParams &, const RowOpts &, hipStream_t);
+void launch_extend_retry(bool, const Db &, const ExtParams &, const RowOpts &, hipStream_t);
+void launch_later_rounds(bool, const Db &, const ExtParams &, const RowOpts &, const LaterParams &, Cand *const[2],
+                         uint32_t *const[2], int32_t *const[2], uint32_t *const[2], unsigned long long *, hipStream_t);
 void launch_later_finish(const ExtParams &, const LaterParams &, hipStream_t);
 int row_slot_words_max(bool amb);
 void launch_group(const GroupParams &, int, hipStream_t);
@@ -293,8 +292,56 @@ struct SampleRec {
 static const uint64_t TILE_ALIGN = 1ull << POS_TX_SHIFT;
 static uint64_t align_up(uint64_t x) { return (x + TILE_ALIGN - 1) & ~(TILE_ALIGN - 1); }
 
+// Tuning knobs and test hooks. The environment is read once, when the engine
+// is created (rc_create); a variable changed later does not reach an engine
+// that exists. One line per variable: name (default) and meaning.
+struct Knobs {
+    bool share;           // RC_SHARE (1): 0 = a pair's two directed searches one after the other
+    uint64_t tile_bases;  // RC_TILE_BASES (2^32 - 2^24; at least TILE_ALIGN): a tile's most bases (tests: small tiles)
+    bool tile_split;      // RC_TILE_SPLIT (1): 0 = no split tiles, so no index reuse from tile to tile
+    int ovf_cap0;         // RC_OVF_CAP0 (unset = 0; else at least 1): first HSP overflow buffer size (tests: its retry)
+    int win_words;        // RC_WIN_WORDS (unset = 0; else at least 4): row staging windows of that many words (tests)
+    bool later;           // RC_LATER (1): 0 = extend_kernel runs the deferred searches' later seeds whole
+    int later_rows;       // RC_LATER_ROWS (64): 32 = the later-seed rounds run the 32-lane pass first
+    uint64_t later_cap;   // RC_LATER_CAP (24 M, at least 1): searches the later-seed rounds hold states for
+    bool rbh_two_pass;    // RC_RBH_TWO_PASS (unset; any value sets it): always the full second RBH pass
+    int resume;           // RC_RESUME (unset = -1: by the last run's overflows): 1 = always save 32-lane states, 0 = never
+    bool wide;            // RC_WIDE (1): 0 = what outgrows the 32-lane window goes to the one-wave kernel whole
+    bool row64;           // RC_ROW64 (0): 1 = independent searches: a 64-lane pass over the 32-lane pass's deferrals
+    int seed_pre;         // RC_SEED_PRE (1): the seed kernel's SeedParams::pre_mode; 1 = hit-list pre-test
+    int reuse;            // RC_REUSE (1): 0 = extend_kernel redoes every search's first seed
+    int index_bits_max;   // RC_INDEX_BITS_MAX (28, clamped to [16, 30]): most bucket-table bits of a seed index
+    int dust_waves;       // RC_DUST_WAVES (0 = every resident wave): DUST waves per SIMD
+};
+
+static Knobs read_knobs()
+{
+    const auto env = [](const char *name) -> const char * { return getenv(name); };
+    const auto num = [&](const char *name, int unset) { return env(name) ? atoi(env(name)) : unset; };
+    Knobs k{};
+    k.share = num("RC_SHARE", 1) != 0;
+    k.tile_bases = env("RC_TILE_BASES") ? std::max<uint64_t>(strtoull(env("RC_TILE_BASES"), nullptr, 10), TILE_ALIGN)
+                                        : (1ull << 32) - (1ull << 24);
+    k.tile_split = num("RC_TILE_SPLIT", 1) != 0;
+    k.ovf_cap0 = env("RC_OVF_CAP0") ? std::max(1, num("RC_OVF_CAP0", 1)) : 0;
+    k.win_words = env("RC_WIN_WORDS") ? std::max(4, num("RC_WIN_WORDS", 4)) : 0;
+    k.later = num("RC_LATER", 1) != 0;
+    k.later_rows = num("RC_LATER_ROWS", 64);
+    k.later_cap = env("RC_LATER_CAP") ? (uint64_t)std::max(atoll(env("RC_LATER_CAP")), 1ll) : (24ull << 20);
+    k.rbh_two_pass = env("RC_RBH_TWO_PASS") != nullptr;
+    k.resume = num("RC_RESUME", -1);
+    k.wide = num("RC_WIDE", 1) != 0;
+    k.row64 = num("RC_ROW64", 0) != 0;
+    k.seed_pre = num("RC_SEED_PRE", 1);
+    k.reuse = num("RC_REUSE", 1);
+    k.index_bits_max = std::max(16, std::min(30, num("RC_INDEX_BITS_MAX", 28)));
+    k.dust_waves = num("RC_DUST_WAVES", 0);
+    return k;
+}
+
 struct rc_engine {
     rc_opts o{};
+    Knobs knobs{};
     hipStream_t st = nullptr;
     hipStream_t st2 = nullptr;   // DUST beside the index build
     std::vector<SampleRec> samples;
@@ -341,7 +388,6 @@ struct rc_engine {
     bool tile_direct = false;           // the loaded tile is d_ascii's layout (no gathered copy)
     uint32_t tile_ntx = 0;              // the tile's transcripts (DUST, near-mask index)
     uint32_t tile_nitx = 0;             // ... of its subject samples (the 16-mer index)
-    bool tile_share = false;            // the search mode the loaded tile's index list was built for
     std::vector<uint32_t> tile_tx_first;   // first transcript (in d_tile_tx) of each sample of the tile
     // DUST masks given by rc_set_dust_masks (computed once per sample across
     // shards): word offset of each sample's mask in d_dust_imp, ~0 = not given
@@ -401,7 +447,7 @@ struct rc_engine {
     DBuf<uint64_t> d_ent, d_ent2;   // (k-mer << 32 | position), unsorted / sorted
     // the index sort's scratch (sort.hip): digit histograms + tile counters,
     // the look-back table (zeroed when allocated; tagged by pass epoch)
-    DBuf<uint32_t> d_sort_scratch, d_gen_tile;
+    DBuf<uint32_t> d_sort_scratch;
     DBuf<uint64_t> d_sort_status;
     uint32_t sort_epoch = 0;
     DBuf<uint32_t> d_bucket;
@@ -430,6 +476,9 @@ struct rc_engine {
     DBuf<Cand> d_lvc0, d_lvc1;
     DBuf<uint32_t> d_llist0, d_llist1, d_lact0, d_lact1, d_lfull0, d_lfull1;
     DBuf<unsigned long long> d_lcnt;
+    // both directed searches of a pair from one candidate set (query = the
+    // lower sample), unless spec 5b or RC_SHARE=0 (one after
+    // the other); fixed when the engine is created
     bool share = false;
     DBuf<DRow> d_rows_tmp;
     DBuf<DEdge> d_edges_tmp;
@@ -497,14 +546,6 @@ static int wait_st(rc_engine *e)
     return RC_OK;
 }
 
-// Both directed searches of a pair from one candidate set (query = the lower
-// sample), unless spec 5b or RC_SHARE=0 (one after the other)
-static bool share_mode(const rc_engine *e)
-{
-    const char *sv = getenv("RC_SHARE");
-    return !e->o.symmetric && !(sv && atoi(sv) == 0);
-}
-
 extern "C" {
 
 void rc_default_opts(rc_opts *o)
@@ -550,6 +591,8 @@ int rc_create(const rc_opts *opts, rc_engine **out)
     if (opts->device < 0 || opts->device >= ndev) return fail(RC_E_ARG, "bad device ordinal");
     rc_engine *e = new rc_engine();
     e->o = *opts;
+    e->knobs = read_knobs();
+    e->share = !e->o.symmetric && e->knobs.share;
     if (hipSetDevice(e->o.device) != hipSuccess || hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&e->st2, hipStreamNonBlocking) != hipSuccess) {
         delete e;
@@ -937,7 +980,7 @@ static int upload(rc_engine *e)
     CHK(up(e->d_thr, thr));
     CHK(up(e->d_bits10, b10));
     CHK(e->d_status.ensure(4));
-    CHK(e->d_count.ensure(16));
+    CHK(e->d_count.ensure(DC_N));
     HIPCHK(hipStreamSynchronize(e->st));
     e->tile_loaded = -1;
     e->uploaded = true;
@@ -962,18 +1005,11 @@ static double ev_ms(rc_engine *e, int a, int b)
 // working copy (positions relative to the tile, < 2^32) and indexed together,
 // and the directed searches between them. A shard's pairs form a rectangle
 // [a0, a1) x [b0, b1) of the pair triangle; when its samples fit one tile
-// (rc_opts-independent cap RC_TILE_BASES, default 2^32 - 2^24 bases) the
+// (rc_opts-independent cap Knobs::tile_bases, default 2^32 - 2^24 bases) the
 // shard is one tile, else the a- and b-ranges are cut into chunks of at most
 // half the cap and every (a chunk, b chunk) with pairs is a tile. Each pass
 // appends its HSPs to the shard's store; reciprocal best hits then run over
 // all the shard's pairs.
-
-static uint64_t tile_cap()
-{
-    const char *v = getenv("RC_TILE_BASES");   // test knob: force small tiles
-    if (v) return std::max<uint64_t>(strtoull(v, nullptr, 10), TILE_ALIGN);
-    return (1ull << 32) - (1ull << 24);
-}
 
 static void plan_tiles(rc_engine *e)
 {
@@ -982,7 +1018,7 @@ static void plan_tiles(rc_engine *e)
     for (uint64_t p = e->pair0; p < e->pair1; p++) pairs.push_back({e->pair_a[p], e->pair_b[p]});
     if (pairs.empty()) return;
     auto bases = [&](int s) { return align_up(e->samples[s].nbases); };
-    const uint64_t cap = tile_cap();
+    const uint64_t cap = e->knobs.tile_bases;
     std::vector<int> A, B, U;
     for (auto &pr : pairs) {
         A.push_back(pr.first);
@@ -1012,7 +1048,7 @@ static void plan_tiles(rc_engine *e)
     const bool multi = ub > cap;
     const auto CA = !multi ? std::vector<std::vector<int>>{U} : chunks(A, cap / 2);
     const auto CB = !multi ? std::vector<std::vector<int>>{U} : chunks(B, cap / 2);
-    const bool no_split = getenv("RC_TILE_SPLIT") && atoi(getenv("RC_TILE_SPLIT")) == 0;   // (per plan: tests flip it)
+    const bool no_split = !e->knobs.tile_split;
     uint64_t amax = 0;
     for (size_t j = 0; j < CB.size(); j++)
         for (size_t i = 0; i < CA.size(); i++) {
@@ -1084,8 +1120,8 @@ static int load_tile(rc_engine *e, int ti)
     e->tile_direct = direct;
     // the 16-mer index holds the tile's subject samples only: the b of each
     // pair (shared searches and spec 5b: query = the lower sample), or both
-    const bool share = share_mode(e);
-    if (e->tile_loaded == ti && e->tile_share == share) return RC_OK;
+    const bool share = e->share;
+    if (e->tile_loaded == ti) return RC_OK;
     std::vector<char> subj(N, 0);
     for (auto &pr : T.pairs) {
         subj[pr.second] = 1;
@@ -1158,7 +1194,6 @@ static int load_tile(rc_engine *e, int ti)
     e->tile_npos = npos;
     e->tile_ntx = n_ttx;
     e->tile_nitx = n_itx;
-    e->tile_share = share;
     // the packed working copy's source: d_ascii itself or a gathered copy
     if (!direct) {
         CHK(e->d_tile_ascii.ensure(total + 64));
@@ -1177,33 +1212,12 @@ static int load_tile(rc_engine *e, int ti)
 // Sort index entries ent[0, npos) on key bits [bb, 64) into ent2 and build the
 // bucket table over the top k-mer bits: about one bucket per entry (times
 // 2^extra), at most 2^28 (RC_INDEX_BITS_MAX; 28 measured best at C3 -- a 1 GiB
-// table instead of 4 GiB, same seed-kernel time)
-// the first pass's key generator (sort.hip KeyGen): keys from the packed
-// sequence instead of the fill's entry array
-struct GenArgs {
-    const TxInfo *tx;
-    const uint64_t *koff;
-    const uint64_t *F;
-    uint32_t n_tx;
-};
+// table instead of 4 GiB, same seed-kernel time). counted: the fill left the
+// sort's segment histograms in d_sort_scratch.
 static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, uint64_t npos, unsigned bb, int extra,
-                      DBuf<uint32_t> &bucket, int &bits_out, const std::function<int()> &after_prep = nullptr,
-                      bool counted = false, const GenArgs *gen = nullptr)
+                      DBuf<uint32_t> &bucket, int &bits_out, bool counted = false)
 {
-    static const bool lib = getenv("RC_SORT") && !strcmp(getenv("RC_SORT"), "rocprim");
-    bool prepped = false;   // after_prep runs exactly once, also for an empty index
-    if (lib) {   // A/B only: rocPRIM's onesweep
-        // (rocPRIM sorts up to 2^20 items with a merge sort that did not keep
-        // the input order for a partial bit range: there, all 64 bits -- the
-        // same result, positions are unique)
-        const unsigned lb = bb == 32 && npos <= (1ull << 20) ? 0u : bb;
-        prepped = true;
-        if (after_prep) CHK(after_prep());
-        size_t tmp = 0;
-        HIPCHK(rocprim::radix_sort_keys(nullptr, tmp, ent.p, ent2.p, (size_t)npos, lb, 64u, e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::radix_sort_keys(e->d_tmp.p, tmp, ent.p, ent2.p, (size_t)npos, lb, 64u, e->st));
-    } else if (npos) {
+    if (npos) {
         // sort.hip: 8-bit LSD passes ping-ponging between the two buffers;
         // the result must end in ent2
         if (npos > 0xFFFFFFFFull) return fail(RC_E_LIMIT, "more than 2^32 index entries");
@@ -1213,27 +1227,18 @@ static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, u
             CHK(e->d_sort_status.ensure(words));
             HIPCHK(hipMemsetAsync(e->d_sort_status.p, 0, words * sizeof(uint64_t), e->st));
         }
-        int prc = RC_OK;
-        if (gen) CHK(e->d_gen_tile.ensure(os_gen_tile_words(npos)));
+        // (no callback after the table kernels, no key generator: keys come from the entry array)
         const bool in_alt = os_sort_keys(ent.p, ent2.p, npos, (int)bb, e->d_sort_scratch.p, e->d_sort_status.p,
-                                         e->sort_epoch, e->st, [&]() {
-                                             prepped = true;
-                                             if (after_prep) prc = after_prep();
-                                         }, counted, gen ? gen->tx : nullptr, gen ? gen->koff : nullptr,
-                                         gen ? gen->F : nullptr, gen ? gen->n_tx : 0u,
-                                         gen ? e->d_gen_tile.p : nullptr);
-        CHK(prc);
+                                         e->sort_epoch, e->st, nullptr, counted, nullptr, nullptr, nullptr, 0u,
+                                         nullptr);
         HIPCHK(hipGetLastError());
         if (!in_alt) {
             std::swap(ent.p, ent2.p);
             std::swap(ent.cap, ent2.cap);
         }
     }
-    if (!prepped && after_prep) CHK(after_prep());
-    const char *ibv = getenv("RC_INDEX_BITS_MAX");
-    const int bmax = ibv ? std::max(16, std::min(30, atoi(ibv))) : 28;
     int bits = 16;
-    while (bits < bmax && (1ull << bits) < (npos << extra)) bits++;
+    while (bits < e->knobs.index_bits_max && (1ull << bits) < (npos << extra)) bits++;
     bits_out = bits;
     CHK(bucket.ensure((1ull << bits) + 1));
     launch_bucket_fill(ent2.p, npos, bits, bucket.p, e->st);
@@ -1244,7 +1249,7 @@ static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, u
 // slots koff / kpos (closed form when no base is ambiguous) give the order.
 static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64_t npos, const uint64_t *kpos,
                           DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, DBuf<uint32_t> &bucket, int &bits_out,
-                          uint64_t &n_out, const std::function<int()> &after_fill = nullptr)
+                          uint64_t &n_out)
 {
     const bool amb = e->has_amb;
     const uint64_t *offs = kpos;
@@ -1267,36 +1272,26 @@ static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64
     CHK(ent2.ensure(std::max<uint64_t>(npos, 1)));
     // without ambiguity codes the fill also counts the sort's segment
     // histograms (sort.hip), so the sort does not read the keys to count them
-    static const bool lib = getenv("RC_SORT") && !strcmp(getenv("RC_SORT"), "rocprim");
-    const bool counted = !amb && !lib && npos > 0 && npos <= 0xFFFFFFFFull;
-    // RC_GEN=1: the sort's first pass computes the keys from the sequence
-    // instead of reading the entry array the fill writes (measured slower:
-    // index phase 61.1 vs 57.9 ms at C3 -- the per-key transcript search and
-    // sequence windows cost more than the 25.6 GB of traffic they save)
-    static const bool genv = getenv("RC_GEN") && atoi(getenv("RC_GEN")) == 1;
-    const bool gen = counted && genv && n_tx;
-    const GenArgs ga{txl, offs, e->d_F.p + FRONT_PAD, n_tx};
+    const bool counted = !amb && npos > 0 && npos <= 0xFFFFFFFFull;
     if (counted) {
         CHK(e->d_sort_scratch.ensure(os_scratch_words(npos)));
-        os_fill_hist(txl, n_tx, e->d_F.p + FRONT_PAD, offs, gen ? nullptr : ent.p, npos, e->d_sort_scratch.p, e->st);
+        os_fill_hist(txl, n_tx, e->d_F.p + FRONT_PAD, offs, ent.p, npos, e->d_sort_scratch.p, e->st);
     } else if (n_tx) {
         launch_kmer_fill(amb, txl, n_tx, e->d_F.p + FRONT_PAD, amb ? e->d_AF.p + FRONT_PAD : nullptr, offs, ent.p,
                          e->st);
     }
     // sort on the k-mer (bits 32..63); the fill order is position order and the
-    // radix sort is stable, so positions stay ascending per k-mer. after_fill
-    // (DUST on the second stream) starts once the sort's one-block table
-    // kernels are queued: beside DUST's waves they crawled (4.2 ms vs 14 us).
-    CHK(sort_index(e, ent, ent2, npos, 32u, 0, bucket, bits_out, after_fill, counted, gen ? &ga : nullptr));
+    // radix sort is stable, so positions stay ascending per k-mer
+    CHK(sort_index(e, ent, ent2, npos, 32u, 0, bucket, bits_out, counted));
     n_out = npos;
     return RC_OK;
 }
 
 // The seed index of the loaded tile: every 16-mer position of its subject samples' transcripts.
-static int build_index(rc_engine *e, const std::function<int()> &after_fill = nullptr)
+static int build_index(rc_engine *e)
 {
     return build_index_of(e, e->d_tile_itx.p, e->tile_nitx, e->tile_npos, e->d_kpos_off.p, e->d_ent,
-                          e->d_ent2, e->d_bucket, e->index_bits, e->n_index, after_fill);
+                          e->d_ent2, e->d_bucket, e->index_bits, e->n_index);
 }
 
 // Shared searches with DUST: the reverse pass's index. A reverse search whose
@@ -1480,8 +1475,7 @@ static int reverse_pass(rc_engine *e, int ti, const Db &db, const Index &ixm, ui
             S.iso_n = ioff[ri + 1] - ioff[ri];
             S.word = e->o.word_size;
             S.stride = e->o.word_size - W16 + 1;
-            const char *pm = getenv("RC_SEED_PRE");
-            S.pre_mode = pm ? atoi(pm) : 1;
+            S.pre_mode = e->knobs.seed_pre;
             S.rev = 1;
             S.tx_pos = e->d_tx_pos.p;
             S.iso_pre_g = e->d_iso_pre.p;
@@ -1581,9 +1575,6 @@ static int grow_hsp(rc_engine *e, uint64_t n)
     return RC_OK;
 }
 
-// One alignment pass over tile ti: pack, DUST, index, seeds (one launch per
-// run of query samples), extension, and the (query gene, subject sample) HSP
-// groups appended to the shard's store.
 // The loaded tile's packed working copy (FRONT_PAD zero words in front, zero
 // words behind); ev[0] marks the start of the packing.
 static int pack_tile(rc_engine *e)
@@ -1618,8 +1609,7 @@ static int dust_samples(rc_engine *e, const std::vector<int> &ss, hipStream_t st
     const uint32_t dblocks = 256 * 28;   // at least the resident waves of the chunk kernel (<= 7 per SIMD): their scratch
     CHK(e->d_dust_scratch.ensure(dust_scratch_words(dblocks)));
     CHK(e->d_dust_events.ensure(dust_event_words(dblocks)));
-    const char *dwv = getenv("RC_DUST_WAVES");
-    const int dwaves = dwv ? atoi(dwv) : 0;   // 0: every resident wave (measured best; 1-3 starve DUST)
+    const int dwaves = e->knobs.dust_waves;   // 0: every resident wave (measured best; 1-3 starve DUST)
     int f = -1, l = -1;
     auto flush = [&]() {
         if (f >= 0) {
@@ -1642,16 +1632,39 @@ static int dust_samples(rc_engine *e, const std::vector<int> &ss, hipStream_t st
     return RC_OK;
 }
 
-static int align_tile(rc_engine *e, int ti)
+// ------------------------------------------------------------------------
+// one alignment pass over a tile (align_tile): its stages, in order
+// ------------------------------------------------------------------------
+
+// What the stages share
+struct TileCtx {
+    int ti = 0;
+    std::vector<std::pair<int, int>> runs;   // runs of consecutive query samples: one seed launch each
+    std::vector<uint32_t> rg0, rg1;          // per run: its genes [rg0, rg1)
+    std::vector<uint32_t> ioff;              // ... its slice of d_iso_list
+    std::vector<size_t> gcb, cnb;            // ... its slice of the (gene, sample) arrays, of the group counts
+    int tw = 0;                              // mask words per query sample
+    Db db{};
+    Index ix{}, ixm{};                       // the tile's seed index; the reverse pass's (masked transcripts only)
+    uint32_t n_rs = 0;                       // reverse-only seeds (reverse_pass)
+    uint64_t n_cand = 0;
+    bool later_on = false;                   // the later-seed rounds ran: lat holds their parameters
+    LaterParams lat{};
+};
+
+static RowOpts row_opts(const rc_engine *e) { return RowOpts{e->knobs.wide, e->knobs.row64, e->knobs.later_rows}; }
+
+// Stage 1: the tile's tables and packed copy, DUST masks (on the second
+// stream), the seed index (built, or the previous tile's) and, for shared
+// searches with DUST, the near-mask index. Events ev[0] .. ev[2].
+static int index_stage(rc_engine *e, int ti)
 {
     {
         const double t0 = wall_ms();
         CHK(load_tile(e, ti));
         e->tm.load_ms += wall_ms() - t0;
     }
-    const int N = (int)e->samples.size();
     const uint64_t total = e->tile_total;
-    const uint32_t n_genes = (uint32_t)e->gene_sample.size();
     CHK(pack_tile(e));
     const bool dust = e->o.dust_level > 0;
     // a split tile of the b chunk the previous tile had: its 16-mer index
@@ -1660,7 +1673,7 @@ static int align_tile(rc_engine *e, int ti)
     // (only while the index holds the b part alone: with one directed search
     // at a time -- RC_SHARE=0, not spec 5b -- it holds the a part's samples
     // too, and they differ from tile to tile)
-    const bool b_only_index = share_mode(e) || e->o.symmetric;
+    const bool b_only_index = e->share || e->o.symmetric;
     const bool reuse = b_only_index && TT.bchunk >= 0 && TT.bchunk == e->idx_bchunk && TT.bstart == e->idx_bstart &&
                        e->d_dmask.cap >= (total >> 6) + 4;
     const uint64_t dtot = reuse ? TT.bstart : total;   // masks cleared: the a part only when reusing
@@ -1689,79 +1702,72 @@ static int align_tile(rc_engine *e, int ti)
     // DUST masks of the tile's transcripts (the query side), bit per base, on
     // the second stream: a compute-bound scan beside the HBM-bound index
     // build, started with the fill (r03, hand-written sort and DUST: index
-    // phase 55.7 vs 58.1 ms at C3 when started after the sort's table kernels;
-    // RC_DUST_EARLY=0 starts it there).
-    auto start_dust = [&]() -> int {
+    // phase 55.7 vs 58.1 ms at C3 when started after the sort's table kernels)
+    if (dust) {
         HIPCHK(hipEventRecord(e->evd[2], e->st));
         HIPCHK(hipStreamWaitEvent(e->st2, e->evd[2], 0));
         HIPCHK(hipEventRecord(e->evd[0], e->st2));
         CHK(dust_samples(e, dust_here, e->st2));
         HIPCHK(hipEventRecord(e->evd[1], e->st2));
-        return RC_OK;
-    };
-    const char *dev = getenv("RC_DUST_EARLY");
-    const int dmode = dev ? atoi(dev) : 1;   // 1: beside the fill (default), 0: after the sort's table kernels, 2: before the index
-    const bool dust_early = dmode != 0;
-    if (dust && dmode == 2) {
-        // DUST alone on the engine's stream, then the index build alone
-        HIPCHK(hipEventRecord(e->evd[0], e->st));
-        CHK(dust_samples(e, dust_here, e->st));
-        HIPCHK(hipEventRecord(e->evd[1], e->st));
-    } else if (dust && dust_early) {
-        CHK(start_dust());
     }
-    if (reuse) {
-        if (dust && !dust_early) CHK(start_dust());
+    if (reuse)
         e->tm.index_reused += 1.0;
-    } else {
-        CHK(build_index(e, dust && !dust_early ? std::function<int()>(start_dust) : nullptr));
-    }
+    else
+        CHK(build_index(e));
     e->idx_bchunk = TT.bchunk;
     e->idx_bstart = TT.bstart;
     HIPCHK(hipGetLastError());
     if (dust) HIPCHK(hipStreamWaitEvent(e->st, e->evd[1], 0));
-    e->share = share_mode(e);   // (load_tile built the index list for it)
     // shared searches with DUST: reverse-search runs with no usable word of
     // the forward query inside come from a reverse pass over a near-mask index
-    const bool revpass = e->share && dust;
-    if (revpass) CHK(build_masked_index(e));
+    if (e->share && dust) CHK(build_masked_index(e));
     HIPCHK(hipEventRecord(e->ev[2], e->st));
+    return RC_OK;
+}
 
+// Stage 2: the tile's directed searches as runs of query samples, their
+// tables on the device, first guesses of the seed / candidate / HSP-overflow
+// capacities, and the kernels' views of the tile (db, ix, ixm)
+static int plan_stage(rc_engine *e, TileCtx &C)
+{
+    const int N = (int)e->samples.size();
     std::vector<uint64_t> tmask;
-    std::vector<std::pair<int, int>> runs;
-    tile_plan(e, ti, tmask, runs);
-    const size_t R = runs.size(), RT = R;
-    const int tw = mask_words(N);
+    auto &runs = C.runs;
+    tile_plan(e, C.ti, tmask, runs);
+    const size_t R = runs.size();
+    const int tw = C.tw = mask_words(N);
     std::vector<int32_t> trange;
     mask_ranges(tmask, N, trange);
     CHK(e->d_tmask.ensure(tmask.size()));
     CHK(e->d_trange.ensure(trange.size()));
     HIPCHK(hipMemcpyAsync(e->d_tmask.p, tmask.data(), tmask.size() * 8, hipMemcpyHostToDevice, e->st));
     HIPCHK(hipMemcpyAsync(e->d_trange.p, trange.data(), trange.size() * 4, hipMemcpyHostToDevice, e->st));
-    // per run: its genes [g0, g1) and its slice of the (gene, sample) arrays
-    std::vector<uint32_t> rg0(RT), rg1(RT);
-    std::vector<uint32_t> ilist, ioff(1, 0);
-    std::vector<size_t> gcb(RT + 1, 0), cnb(R + 1, 0);
-    for (size_t r = 0; r < RT; r++) {
-        rg0[r] = e->sample_gene_begin[runs[r].first];
-        rg1[r] = e->sample_gene_begin[runs[r].second];
-        gcb[r + 1] = gcb[r] + (size_t)(rg1[r] - rg0[r]) * N;
-        if (r < R) cnb[r + 1] = cnb[r] + (size_t)(rg1[r] - rg0[r]) * N + 1;
-        ioff.push_back(ioff.back() + iso_genes(e, rg0[r], rg1[r], ilist));
+    std::vector<uint32_t> ilist;
+    C.rg0.assign(R, 0);
+    C.rg1.assign(R, 0);
+    C.ioff.assign(1, 0);
+    C.gcb.assign(R + 1, 0);
+    C.cnb.assign(R + 1, 0);
+    for (size_t r = 0; r < R; r++) {
+        C.rg0[r] = e->sample_gene_begin[runs[r].first];
+        C.rg1[r] = e->sample_gene_begin[runs[r].second];
+        C.gcb[r + 1] = C.gcb[r] + (size_t)(C.rg1[r] - C.rg0[r]) * N;
+        C.cnb[r + 1] = C.cnb[r] + (size_t)(C.rg1[r] - C.rg0[r]) * N + 1;
+        C.ioff.push_back(C.ioff.back() + iso_genes(e, C.rg0[r], C.rg1[r], ilist));
     }
     CHK(e->d_iso_list.ensure(std::max<size_t>(ilist.size(), 1)));
     if (!ilist.empty())
         HIPCHK(hipMemcpyAsync(e->d_iso_list.p, ilist.data(), ilist.size() * 4, hipMemcpyHostToDevice, e->st));
-    CHK(e->d_gc_off.ensure(std::max<size_t>(gcb[RT], 1)));
-    CHK(e->d_gc_cnt.ensure(std::max<size_t>(gcb[RT], 1)));
-    CHK(e->d_gcount.ensure(std::max<size_t>(cnb[R], 1)));
-    CHK(e->d_gscan.ensure(std::max<size_t>(cnb[R], 1)));
+    CHK(e->d_gc_off.ensure(std::max<size_t>(C.gcb[R], 1)));
+    CHK(e->d_gc_cnt.ensure(std::max<size_t>(C.gcb[R], 1)));
+    CHK(e->d_gcount.ensure(std::max<size_t>(C.cnb[R], 1)));
+    CHK(e->d_gscan.ensure(std::max<size_t>(C.cnb[R], 1)));
     CHK(e->d_shard_cnt.ensure(2 * NSHARD));
     CHK(e->d_shard_prefix.ensure(NSHARD + 1));
     {
         // (query gene, subject sample) searches of the tile
         uint64_t nb = 1;
-        for (size_t r = 0; r < RT; r++)
+        for (size_t r = 0; r < R; r++)
             for (int q = runs[r].first; q < runs[r].second; q++) {
                 uint64_t ns = 0;
                 for (int w = 0; w < tw; w++) ns += (uint64_t)__builtin_popcountll(tmask[(size_t)tw * q + w]);
@@ -1770,27 +1776,84 @@ static int align_tile(rc_engine *e, int ti)
         e->seed_cap = std::max<uint64_t>(e->seed_cap, nb * 16 / NSHARD + 4096);
         e->cand_cap = std::max<uint64_t>(e->cand_cap, nb * 2 / NSHARD + 1024);
         // (RC_OVF_CAP0: a smaller first guess, for tests of the overflow retry)
-        const char *oc = getenv("RC_OVF_CAP0");
-        e->ovf_cap = std::max<uint64_t>(e->ovf_cap, oc ? (uint64_t)std::max(1, atoi(oc)) : nb / 4 + 1024);
+        const int oc = e->knobs.ovf_cap0;
+        e->ovf_cap = std::max<uint64_t>(e->ovf_cap, oc ? (uint64_t)oc : nb / 4 + 1024);
     }
-    Db db = make_db(e);
-    Index ix;
-    ix.ent = e->d_ent2.p;
-    ix.bucket = e->d_bucket.p;
-    ix.pos_tx = e->d_pos_tx.p;
-    ix.bits = e->index_bits;
-    Index ixm = ix;   // the reverse pass's: masked transcripts only
-    ixm.ent = e->d_ment2.p;
-    ixm.bucket = e->d_mbucket.p;
-    ixm.bits = e->mindex_bits;
-    // --- seeds ---
+    C.db = make_db(e);
+    C.ix.ent = e->d_ent2.p;
+    C.ix.bucket = e->d_bucket.p;
+    C.ix.pos_tx = e->d_pos_tx.p;
+    C.ix.bits = e->index_bits;
+    C.ixm = C.ix;
+    C.ixm.ent = e->d_ment2.p;
+    C.ixm.bucket = e->d_mbucket.p;
+    C.ixm.bits = e->mindex_bits;
+    CHK(e->d_count.ensure(DC_N));
+    return RC_OK;
+}
+
+// The nb (gene, sample) passes of run S (listed in d_big_out) whose seeds
+// overflow LDS: global-memory passes, at most BIG_CHUNK workgroups per
+// launch; entries that overflow big_cap too are rerun with twice the scratch.
+// again: the seed or candidate buffers overflowed.
+static int seed_big_passes(rc_engine *e, const TileCtx &C, const SeedParams &S, unsigned long long nb, bool &again)
+{
+    const uint64_t BIG_CHUNK = 2048;
+    unsigned long long *const big_retry_n = e->d_count.p + DC_BIG_RETRY;
+    uint64_t *list = e->d_big_out.p;
+    while (!again && nb) {
+        if ((uint64_t)e->big_cap > (1ull << 22))
+            return fail(RC_E_LIMIT, "a (query gene, subject sample) pass has more than 2^22 seeds");
+        const uint64_t chunk = std::min<uint64_t>(nb, BIG_CHUNK);
+        CHK(e->d_big_list.ensure(nb));
+        CHK(e->d_big_retry.ensure(nb));
+        CHK(e->d_big_seeds.ensure(chunk * e->big_cap));
+        CHK(e->d_big_seg.ensure(chunk * (e->big_cap + 1)));
+        CHK(e->d_big_segT.ensure(chunk * e->big_cap));
+        if (list != e->d_big_list.p)
+            HIPCHK(hipMemcpyAsync(e->d_big_list.p, list, nb * 8, hipMemcpyDeviceToDevice, e->st));
+        HIPCHK(hipMemsetAsync(big_retry_n, 0, sizeof(unsigned long long), e->st));
+        SeedParams B = S;
+        B.big_retry = e->d_big_retry.p;
+        B.big_list_cap = nb;
+        B.big_cap = e->big_cap;
+        B.big_seeds = e->d_big_seeds.p;
+        B.big_seg = e->d_big_seg.p;
+        B.big_segT = e->d_big_segT.p;
+        for (uint64_t c0 = 0; c0 < nb; c0 += chunk) {
+            B.big_list = e->d_big_list.p + c0;
+            launch_seed_big(e->has_amb, C.db, C.ix, B, (uint32_t)std::min<uint64_t>(chunk, nb - c0), e->st);
+            HIPCHK(hipGetLastError());
+        }
+        unsigned int status = 0;
+        unsigned long long nr = 0;
+        HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&nr, big_retry_n, sizeof nr, hipMemcpyDeviceToHost, e->st));
+        CHK(wait_st(e));
+        if (status & 16u)
+            return fail(RC_E_LIMIT, "a candidate's first seed of a directed search is past seed 65534");
+        again = (status & 1u) != 0;
+        nb = nr;
+        // the retry entries become the next list (buffers swapped, not copied)
+        std::swap(e->d_big_list.p, e->d_big_retry.p);
+        std::swap(e->d_big_list.cap, e->d_big_retry.cap);
+        list = e->d_big_list.p;
+        if (nb) e->big_cap *= 2;
+    }
+    return RC_OK;
+}
+
+// Stage 3: seeds and candidates of every run (the reverse pass first, for
+// shared searches with DUST), again with larger buffers while one overflows;
+// then the candidates' shard prefix. Events ev[3], ev[9].
+static int seed_stage(rc_engine *e, TileCtx &C)
+{
+    const size_t R = C.runs.size();
     std::vector<unsigned long long> shard_cnt(2 * NSHARD);
-    CHK(e->d_count.ensure(34));
-    unsigned long long *big_n = e->d_count.p + 12, *big_retry_n = e->d_count.p + 13;
+    unsigned long long *const big_n = e->d_count.p + DC_BIG;
     uint64_t n_big = 0;
     HIPCHK(hipEventRecord(e->ev[3], e->st));
-    uint32_t n_rs = 0;
-    if (revpass && e->n_mindex) CHK(reverse_pass(e, ti, db, ixm, n_rs));
+    if (e->share && e->o.dust_level > 0 && e->n_mindex) CHK(reverse_pass(e, C.ti, C.db, C.ixm, C.n_rs));
     for (int attempt = 0;; attempt++) {
         if (attempt == 6) return fail(RC_E_NOMEM, "seed/candidate buffers kept overflowing");
         if (e->seed_cap * NSHARD > 0xFFFFFFFFull || e->cand_cap * NSHARD > 0xFFFFFFFFull)
@@ -1798,66 +1861,66 @@ static int align_tile(rc_engine *e, int ti)
         CHK(e->d_seeds.ensure(e->seed_cap * NSHARD));
         CHK(e->d_cands.ensure(e->cand_cap * NSHARD));
         if (e->share) CHK(e->d_list2.ensure(e->cand_cap * NSHARD));
-        HIPCHK(hipMemsetAsync(e->d_count.p + 16, 0, sizeof(unsigned long long), e->st));
+        HIPCHK(hipMemsetAsync(e->d_count.p + DC_LIST2, 0, sizeof(unsigned long long), e->st));
         CHK(e->d_big_out.ensure(e->big_list_cap));
         HIPCHK(hipMemsetAsync(e->d_shard_cnt.p, 0, 2 * NSHARD * sizeof(unsigned long long), e->st));
         HIPCHK(hipMemsetAsync(e->d_status.p, 0, 4 * sizeof(unsigned int), e->st));
-        if (gcb[RT]) HIPCHK(hipMemsetAsync(e->d_gc_cnt.p, 0, gcb[RT] * 4, e->st));
+        if (C.gcb[R]) HIPCHK(hipMemsetAsync(e->d_gc_cnt.p, 0, C.gcb[R] * 4, e->st));
         CHK(e->d_prof.ensure(10));
         HIPCHK(hipMemsetAsync(e->d_prof.p, 0, 10 * sizeof(unsigned long long), e->st));
+        // what every run of this attempt shares
+        SeedParams S0{};
+        S0.word = e->o.word_size;
+        S0.stride = e->o.word_size - W16 + 1;
+        S0.pre_mode = e->knobs.seed_pre;
+        S0.sym = e->o.symmetric;
+        S0.share = e->share ? 1 : 0;
+        S0.tx_pos = e->d_tx_pos.p;
+        S0.iso_pre_g = e->d_iso_pre.p;
+        S0.rs_rec = e->d_rseeds.p;
+        S0.rs_key = e->d_rs_key.p;
+        S0.rs_idx = e->d_rs_idx.p;
+        S0.rs_n = C.n_rs;
+        S0.list2 = e->d_list2.p;
+        S0.list2_n = e->d_count.p + DC_LIST2;
+        S0.seeds = e->d_seeds.p;
+        S0.seed_cap = e->seed_cap;
+        S0.seed_count = e->d_shard_cnt.p;
+        S0.cands = e->d_cands.p;
+        S0.cand_cap = e->cand_cap;
+        S0.cand_count = e->d_shard_cnt.p + NSHARD;
+        S0.tmask = e->d_tmask.p;
+        S0.tmw = C.tw;
+        S0.trange = e->d_trange.p;
+        S0.xbits = e->xbits;
+        S0.max_iso = max_iso(e->xbits);
+        S0.status = e->d_status.p;
+        S0.big_out = e->d_big_out.p;
+        S0.big_n = big_n;
+        S0.big_retry_n = e->d_count.p + DC_BIG_RETRY;
+        S0.big_list_cap = e->big_list_cap;
+        S0.prof = e->d_prof.p;
         bool again = false;
         n_big = 0;
-        for (size_t r = 0; r < RT && !again; r++) {
-            HIPCHK(hipMemsetAsync(big_n, 0, 2 * sizeof(unsigned long long), e->st));
-            SeedParams S{};
-            S.word = e->o.word_size;
-            S.stride = e->o.word_size - W16 + 1;
-            {
-                const char *pm = getenv("RC_SEED_PRE");   // A/B knob; 1 = hit-list pre-test
-                S.pre_mode = pm ? atoi(pm) : 1;
-            }
-            S.sym = e->o.symmetric;
-            S.share = e->share ? 1 : 0;
-            S.tx_pos = e->d_tx_pos.p;
-            S.iso_pre_g = e->d_iso_pre.p;
-            S.rs_rec = e->d_rseeds.p;
-            S.rs_key = e->d_rs_key.p;
-            S.rs_idx = e->d_rs_idx.p;
-            S.rs_n = n_rs;
-            S.list2 = e->d_list2.p;
-            S.list2_n = e->d_count.p + 16;
-            S.gene_begin = rg0[r];
-            S.gene_end = rg1[r];
-            if (n_rs) {
-                CHK(e->d_rs_range.ensure((size_t)2 * (rg1[r] - rg0[r]) + 2));
-                launch_rs_range(e->d_rs_key.p, n_rs, rg0[r], rg1[r], e->d_rs_range.p, e->st);
+        for (size_t r = 0; r < R && !again; r++) {
+            // (DC_BIG and DC_BIG_RETRY)
+            HIPCHK(hipMemsetAsync(big_n, 0, (DC_DEFER2 - DC_BIG) * sizeof(unsigned long long), e->st));
+            SeedParams S = S0;
+            S.gene_begin = C.rg0[r];
+            S.gene_end = C.rg1[r];
+            if (C.n_rs) {
+                CHK(e->d_rs_range.ensure((size_t)2 * (C.rg1[r] - C.rg0[r]) + 2));
+                launch_rs_range(e->d_rs_key.p, C.n_rs, C.rg0[r], C.rg1[r], e->d_rs_range.p, e->st);
                 S.rs_range = e->d_rs_range.p;
             }
-            S.iso_list = e->d_iso_list.p + ioff[r];
-            S.iso_n = ioff[r + 1] - ioff[r];
-            S.seeds = e->d_seeds.p;
-            S.seed_cap = e->seed_cap;
-            S.seed_count = e->d_shard_cnt.p;
-            S.cands = e->d_cands.p;
-            S.cand_cap = e->cand_cap;
-            S.cand_count = e->d_shard_cnt.p + NSHARD;
-            S.gc_off = e->d_gc_off.p + gcb[r];
-            S.gc_cnt = e->d_gc_cnt.p + gcb[r];
-            S.tmask = e->d_tmask.p;
-            S.tmw = tw;
-            S.trange = e->d_trange.p;
-            S.xbits = e->xbits;
-            S.max_iso = max_iso(e->xbits);
-            S.status = e->d_status.p;
-            S.big_out = e->d_big_out.p;
-            S.big_n = big_n;
-            S.big_retry_n = big_retry_n;
-            S.big_list_cap = e->big_list_cap;
-            S.prof = e->d_prof.p;
-            launch_seed(e->has_amb, db, ix, S, e->st);
+            S.iso_list = e->d_iso_list.p + C.ioff[r];
+            S.iso_n = C.ioff[r + 1] - C.ioff[r];
+            S.gc_off = e->d_gc_off.p + C.gcb[r];
+            S.gc_cnt = e->d_gc_cnt.p + C.gcb[r];
+            launch_seed(e->has_amb, C.db, C.ix, S, e->st);
             HIPCHK(hipGetLastError());
             unsigned int status = 0;
-            unsigned long long nb = 0;   // (big_n: d_count[12], next to the extension's counters [0, 11))
+            unsigned long long nb = 0;
             HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
             HIPCHK(hipMemcpyAsync(&nb, big_n, sizeof nb, hipMemcpyDeviceToHost, e->st));
             CHK(wait_st(e));
@@ -1871,50 +1934,8 @@ static int align_tile(rc_engine *e, int ti)
                 break;
             }
             again = (status & 1u) != 0;
-            // (gene, sample) passes whose seeds overflow LDS: global-memory
-            // passes, at most BIG_CHUNK workgroups per launch; entries that
-            // overflow big_cap too are rerun with twice the scratch
-            const uint64_t BIG_CHUNK = 2048;
-            uint64_t *list = e->d_big_out.p;
             n_big += nb;
-            while (!again && nb) {
-                if ((uint64_t)e->big_cap > (1ull << 22))
-                    return fail(RC_E_LIMIT, "a (query gene, subject sample) pass has more than 2^22 seeds");
-                const uint64_t chunk = std::min<uint64_t>(nb, BIG_CHUNK);
-                CHK(e->d_big_list.ensure(nb));
-                CHK(e->d_big_retry.ensure(nb));
-                CHK(e->d_big_seeds.ensure(chunk * e->big_cap));
-                CHK(e->d_big_seg.ensure(chunk * (e->big_cap + 1)));
-                CHK(e->d_big_segT.ensure(chunk * e->big_cap));
-                if (list != e->d_big_list.p)
-                    HIPCHK(hipMemcpyAsync(e->d_big_list.p, list, nb * 8, hipMemcpyDeviceToDevice, e->st));
-                HIPCHK(hipMemsetAsync(big_retry_n, 0, sizeof(unsigned long long), e->st));
-                SeedParams B = S;
-                B.big_retry = e->d_big_retry.p;
-                B.big_list_cap = nb;
-                B.big_cap = e->big_cap;
-                B.big_seeds = e->d_big_seeds.p;
-                B.big_seg = e->d_big_seg.p;
-                B.big_segT = e->d_big_segT.p;
-                for (uint64_t c0 = 0; c0 < nb; c0 += chunk) {
-                    B.big_list = e->d_big_list.p + c0;
-                    launch_seed_big(e->has_amb, db, ix, B, (uint32_t)std::min<uint64_t>(chunk, nb - c0), e->st);
-                    HIPCHK(hipGetLastError());
-                }
-                unsigned long long nr = 0;
-                HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
-                HIPCHK(hipMemcpyAsync(&nr, big_retry_n, sizeof nr, hipMemcpyDeviceToHost, e->st));
-                CHK(wait_st(e));
-                if (status & 16u)
-                    return fail(RC_E_LIMIT, "a candidate's first seed of a directed search is past seed 65534");
-                again = (status & 1u) != 0;
-                nb = nr;
-                // the retry entries become the next list (buffers swapped, not copied)
-                std::swap(e->d_big_list.p, e->d_big_retry.p);
-                std::swap(e->d_big_list.cap, e->d_big_retry.cap);
-                list = e->d_big_list.p;
-                if (nb) e->big_cap *= 2;
-            }
+            CHK(seed_big_passes(e, C, S, nb, again));
         }
         HIPCHK(hipEventRecord(e->ev[9], e->st));
         HIPCHK(hipMemcpyAsync(shard_cnt.data(), e->d_shard_cnt.p, 2 * NSHARD * 8, hipMemcpyDeviceToHost, e->st));
@@ -1931,12 +1952,170 @@ static int align_tile(rc_engine *e, int ti)
     e->tm.big_passes += (double)n_big;
     std::vector<unsigned long long> prefix(NSHARD + 1, 0);
     for (int i = 0; i < NSHARD; i++) prefix[i + 1] = prefix[i] + shard_cnt[NSHARD + i];
-    const uint64_t n_cand = prefix[NSHARD];
+    C.n_cand = prefix[NSHARD];
     for (int i = 0; i < NSHARD; i++) e->n_seeds += shard_cnt[i];
-    e->n_cands += n_cand;
+    e->n_cands += C.n_cand;
     HIPCHK(hipMemcpyAsync(e->d_shard_prefix.p, prefix.data(), (NSHARD + 1) * 8, hipMemcpyHostToDevice, e->st));
-    // --- extension ---
-    const uint64_t slots = e->cand_cap * NSHARD;
+    return RC_OK;
+}
+
+// The extension kernels' parameters from the engine's buffers (as sized now)
+static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
+{
+    unsigned long long *const cnt = e->d_count.p;
+    ExtParams X{};
+    X.xdrop = e->o.xdrop_half;
+    X.sym = e->o.symmetric;
+    X.max_len = e->max_len;
+    X.thr = e->d_thr.p;
+    X.bits10 = e->d_bits10.p;
+    X.cands = e->d_cands.p;
+    X.seeds = e->d_seeds.p;
+    X.shard_prefix = e->d_shard_prefix.p;
+    X.n_cand = C.n_cand;
+    X.cand_cap = e->cand_cap;
+    X.cand_hsp = e->d_cand_hsp.p;
+    X.cand_nh = e->d_cand_nh.p;
+    X.cand_ovf = e->d_cand_ovf.p;
+    X.ovf = e->d_ovf.p;
+    X.ovf_cap = e->ovf_cap;
+    X.ovf_count = cnt + DC_OVF;
+    X.status = e->d_status.p;
+    X.counters = cnt + DC_COUNTERS;
+    {
+        // row staging slot (u64 words): whole transcripts when the longest
+        // fits the slot the 32-lane kernel has at full occupancy, else
+        // windows of that slot (the windowed instantiation). RC_WIN_WORDS
+        // forces windows of that many words (tests: many refills).
+        const int need = ((e->max_len + 31) >> 5) + 4;
+        const int smax = row_slot_words_max(e->has_amb);
+        const int forced = e->knobs.win_words;
+        X.win = forced ? 1 : (need > smax ? 1 : 0);
+        X.dsw = forced ? std::min(forced, smax) : std::min(need, smax);
+    }
+    X.defer = e->d_defer.p;
+    X.defer_count = cnt + DC_DEFER;
+    X.work = cnt + DC_WORK;
+    X.defer2 = e->d_defer2.p;
+    X.defer2_count = cnt + DC_DEFER2;
+    X.work2 = cnt + DC_WORK2;
+    X.cand_box = e->d_cand_box.p;
+    X.share = e->share ? 1 : 0;
+    X.which = 0;
+    X.dir = 0;
+    X.cand_box2 = e->d_cand_box2.p;
+    X.cand_hsp_r = e->d_cand_hsp_r.p;
+    X.cand_nh_r = e->d_cand_nh_r.p;
+    X.cand_ovf_r = e->d_cand_ovf_r.p;
+    X.defer_r = e->d_defer_r.p;
+    X.defer_r_count = cnt + DC_DEFER_R;
+    X.list2 = e->d_list2.p;
+    X.list2_n = cnt + DC_LIST2;
+    X.work3 = cnt + DC_WORK3;
+    X.wide0 = e->share ? e->d_wide0.p : nullptr;
+    X.wide1 = e->d_wide1.p;
+    X.wide0_n = cnt + DC_WIDE0;
+    X.wide1_n = cnt + DC_WIDE1;
+    {
+        // save overflowing extensions for the 64-lane pass when the last
+        // run had many (C3v: 39 %, C3: 0.002 %): the saving kernel costs
+        // the plain one 7 % (RC_RESUME=1 always, 0 never)
+        const bool on = e->knobs.resume != -1 ? e->knobs.resume == 1 : e->ovf_frac > 0.02;
+        X.resume = e->res_cap && on ? e->d_resume.p : nullptr;
+        X.res_cap = e->res_cap;
+    }
+    X.work_w0 = cnt + DC_WORK_W0;
+    X.work_w1 = cnt + DC_WORK_W1;
+    X.why = cnt + DC_WHY;
+    X.chunk = 8;   // candidates per work grab of the row kernels
+    X.reuse_first = e->knobs.reuse;
+    return X;
+}
+
+// Later-seed rounds over the nsrch = dn0 + dn1 searches first_finish_kernel
+// deferred (forward, reverse): their later seeds on the row kernels; searches
+// past RC_LATER_CAP (default 24 M, 12 GB of state and work) run whole
+static int later_rounds(rc_engine *e, TileCtx &C, const ExtParams &X, uint64_t dn0, uint64_t dn1)
+{
+    const uint64_t nsrch = dn0 + dn1, n = std::min(nsrch, e->knobs.later_cap);
+    CHK(e->d_later.ensure(n * LATER_REC));
+    CHK(e->d_lbox0.ensure(n * BOX_REC));
+    CHK(e->d_lbox1.ensure(n * BOX_REC));
+    CHK(e->d_lvc0.ensure(n));
+    CHK(e->d_lvc1.ensure(n));
+    CHK(e->d_llist0.ensure(n));
+    CHK(e->d_llist1.ensure(n));
+    CHK(e->d_lact0.ensure(n));
+    CHK(e->d_lact1.ensure(n));
+    CHK(e->d_lfull0.ensure(std::max<uint64_t>(dn0, 1)));
+    CHK(e->d_lfull1.ensure(std::max<uint64_t>(dn1, 1)));
+    const size_t nc = (size_t)MAX_HSP * LATER_CNT + LC_N;
+    CHK(e->d_lcnt.ensure(nc));
+    HIPCHK(hipMemsetAsync(e->d_lcnt.p, 0, nc * sizeof(unsigned long long), e->st));
+    LaterParams &lat = C.lat;
+    lat = LaterParams{};
+    lat.state = e->d_later.p;
+    lat.n_search = nsrch;
+    lat.n0 = dn0;
+    lat.n_cap = n;
+    lat.defer0 = X.defer;
+    lat.defer1 = X.defer_r;
+    lat.full0 = e->d_lfull0.p;
+    lat.full1 = e->d_lfull1.p;
+    lat.counters = e->d_lcnt.p + (size_t)MAX_HSP * LATER_CNT;
+    lat.full_n = lat.counters + LC_FULL_N;
+    Cand *const vc[2] = {e->d_lvc0.p, e->d_lvc1.p};
+    uint32_t *const ls[2] = {e->d_llist0.p, e->d_llist1.p};
+    int32_t *const bx[2] = {e->d_lbox0.p, e->d_lbox1.p};
+    uint32_t *const ac[2] = {e->d_lact0.p, e->d_lact1.p};
+    launch_later_rounds(e->has_amb, C.db, X, row_opts(e), lat, vc, ls, bx, ac, e->d_lcnt.p, e->st);
+    HIPCHK(hipGetLastError());
+    C.later_on = true;
+    return RC_OK;
+}
+
+// Stage 5 (RC_ROW_TIMING builds only: their kernels count cycles): the row
+// and seed kernels' cycle counters to stderr; ctr = the counters view. The
+// slots past the view restart.
+static int print_row_timing(rc_engine *e, const unsigned long long *ctr)
+{
+    unsigned long long *const cnt = e->d_count.p;
+    const auto c = [&](int slot) { return (double)ctr[slot - DC_COUNTERS]; };
+    unsigned long long tfs[3] = {0, 0, 0};   // fetches, window slides, extension starts (parts of the transitions)
+    static_assert(DC_T_START - DC_T_FETCH == 2, "the three transition parts are adjacent");
+    HIPCHK(hipMemcpy(tfs, cnt + DC_T_FETCH, sizeof tfs, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(cnt + DC_T_FETCH, 0, sizeof tfs));
+    fprintf(stderr, "row kernel wave-cycles: transitions %.4g (fetches %.4g, window slides %.4g, extension "
+                    "starts %.4g) steps %.4g\n",
+            c(DC_T_TRANS), (double)tfs[0], (double)tfs[1], (double)tfs[2], c(DC_T_STEPS));
+    // 32-lane rows: steps and candidates within a 16-lane window, its slides (profiles/r06_row16)
+    unsigned long long r16[3] = {0, 0, 0};
+    static_assert(DC_T_SL16 == DC_T_C16 + 1, "the two 16-lane slots are cleared together");
+    HIPCHK(hipMemcpy(&r16[0], cnt + DC_T_N16, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&r16[1], cnt + DC_T_C16, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&r16[2], cnt + DC_T_SL16, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(cnt + DC_T_N16, 0, 8));
+    HIPCHK(hipMemset(cnt + DC_T_C16, 0, 16));
+    fprintf(stderr, "row steps before a live span over 14 diagonals %.4g of %.4g; candidates never over 14: "
+                    "%.4g of %.4g; 16-lane window slides %.4g\n", (double)r16[0], c(DC_STEPS),
+            (double)r16[1], c(DC_CANDS), (double)r16[2]);
+    unsigned long long pr[10];
+    HIPCHK(hipMemcpy(pr, e->d_prof.p, sizeof pr, hipMemcpyDeviceToHost));
+    fprintf(stderr, "seed kernel block-cycles: prologue %.4g words: usable %.4g lookup %.4g scan %.4g "
+                    "hits %.4g (loads %.4g pretest %.4g full test %.4g) sort %.4g write %.4g\n",
+            (double)pr[8], (double)pr[9], (double)pr[0], (double)pr[1], (double)(pr[2] + pr[5] + pr[6] + pr[7]),
+            (double)pr[5], (double)pr[6], (double)pr[7], (double)pr[3], (double)pr[4]);
+    return RC_OK;
+}
+
+// Stage 4: the candidates' extensions (row kernels over first seeds, the
+// later-seed rounds, extend_kernel over what they leave); extend_kernel runs
+// again with a larger HSP overflow buffer while that overflows. Events
+// ev[10], ev[11].
+static int extension_stage(rc_engine *e, TileCtx &C)
+{
+    const uint64_t n_cand = C.n_cand, slots = e->cand_cap * NSHARD;
+    unsigned long long *const cnt = e->d_count.p;
     CHK(e->d_cand_hsp.ensure(slots));
     CHK(e->d_cand_nh.ensure(slots));
     CHK(e->d_cand_ovf.ensure(slots));
@@ -1949,114 +2128,38 @@ static int align_tile(rc_engine *e, int ti)
         CHK(e->d_defer_r.ensure(std::max<uint64_t>(n_cand, 1)));
         CHK(e->d_wide0.ensure(std::max<uint64_t>(n_cand, 1)));
         CHK(e->d_wide1.ensure(std::max<uint64_t>(n_cand, 1)));
-        {
-            // room to continue the first 12 M overflowing extensions of a pass
-            // (3.8 GB); later ones start over in the 64-lane pass
-            const char *rv = getenv("RC_RESUME");
-            e->res_cap = (rv && atoi(rv) == 0) ? 0u : (uint32_t)std::min<uint64_t>(n_cand, 12u << 20);
-            if (!(rv && atoi(rv) == 1) && e->ovf_frac <= 0.02) e->res_cap = 0;   // not needed: no buffer
-            if (e->res_cap) CHK(e->d_resume.ensure((size_t)e->res_cap * RES_REC));
-        }
+        // room to continue the first 12 M overflowing extensions of a pass
+        // (3.8 GB); later ones start over in the 64-lane pass
+        e->res_cap = e->knobs.resume == 0 ? 0u : (uint32_t)std::min<uint64_t>(n_cand, 12u << 20);
+        if (e->knobs.resume != 1 && e->ovf_frac <= 0.02) e->res_cap = 0;   // not needed: no buffer
+        if (e->res_cap) CHK(e->d_resume.ensure((size_t)e->res_cap * RES_REC));
     }
     CHK(e->d_defer.ensure(std::max<uint64_t>(n_cand, 1)));
     CHK(e->d_defer2.ensure(std::max<uint64_t>(n_cand, 1)));
-    // later-seed rounds: their parameters once they ran (a retry finishes
-    // the searches again from the states, and extend_kernel takes the lists
-    // of the searches they left whole instead of first_finish_kernel's)
-    bool later_on = false;
-    LaterParams lat{};
+    // later-seed rounds: their parameters (C.lat) once they ran (a retry
+    // finishes the searches again from the states, and extend_kernel takes the
+    // lists of the searches they left whole instead of first_finish_kernel's)
+    C.later_on = false;
     for (int attempt = 0;; attempt++) {
         if (attempt == 4) return fail(RC_E_NOMEM, "HSP overflow buffer kept overflowing");
         CHK(e->d_ovf.ensure(e->ovf_cap));
         if (attempt == 0) {
-            HIPCHK(hipMemsetAsync(e->d_count.p, 0, 12 * sizeof(unsigned long long), e->st));
-            HIPCHK(hipMemsetAsync(e->d_count.p + 14, 0, 2 * sizeof(unsigned long long), e->st));
-            HIPCHK(hipMemsetAsync(e->d_count.p + 17, 0, 2 * sizeof(unsigned long long), e->st));
-            HIPCHK(hipMemsetAsync(e->d_count.p + 20, 0, 7 * sizeof(unsigned long long), e->st));
+            // every slot the extension counts in; the seed stage's (DC_BIG,
+            // DC_BIG_RETRY, DC_LIST2) and the groups' (DC_MBIG) stand
+            HIPCHK(hipMemsetAsync(cnt + DC_OVF, 0, (DC_COUNTERS_END - DC_OVF) * sizeof(unsigned long long), e->st));
+            HIPCHK(hipMemsetAsync(cnt + DC_DEFER2, 0, (DC_LIST2 - DC_DEFER2) * sizeof(unsigned long long), e->st));
+            HIPCHK(hipMemsetAsync(cnt + DC_DEFER_R, 0, (DC_MBIG - DC_DEFER_R) * sizeof(unsigned long long), e->st));
+            HIPCHK(hipMemsetAsync(cnt + DC_WIDE0, 0, (DC_WHY_END - DC_WIDE0) * sizeof(unsigned long long), e->st));
         } else {
             // a retry redoes extend_kernel only: its overflow count restarts,
             // every other counter and list stands
-            HIPCHK(hipMemsetAsync(e->d_count.p, 0, sizeof(unsigned long long), e->st));
+            HIPCHK(hipMemsetAsync(cnt + DC_OVF, 0, sizeof(unsigned long long), e->st));
         }
         HIPCHK(hipMemsetAsync(e->d_status.p, 0, 4 * sizeof(unsigned int), e->st));
-        ExtParams X{};
-        X.xdrop = e->o.xdrop_half;
-        X.sym = e->o.symmetric;
-        X.max_len = e->max_len;
-        X.thr = e->d_thr.p;
-        X.bits10 = e->d_bits10.p;
-        X.cands = e->d_cands.p;
-        X.seeds = e->d_seeds.p;
-        X.shard_prefix = e->d_shard_prefix.p;
-        X.n_cand = n_cand;
-        X.cand_cap = e->cand_cap;
-        X.cand_hsp = e->d_cand_hsp.p;
-        X.cand_nh = e->d_cand_nh.p;
-        X.cand_ovf = e->d_cand_ovf.p;
-        X.ovf = e->d_ovf.p;
-        X.ovf_cap = e->ovf_cap;
-        X.ovf_count = e->d_count.p;
-        X.status = e->d_status.p;
-        X.counters = e->d_count.p + 1;
-        {
-            // row staging slot (u64 words): whole transcripts when the longest
-            // fits the slot the 32-lane kernel has at full occupancy, else
-            // windows of that slot (the windowed instantiation). RC_WIN_WORDS
-            // forces windows of that many words (tests: many refills).
-            const int need = ((e->max_len + 31) >> 5) + 4;
-            const int smax = row_slot_words_max(e->has_amb);
-            const char *wwv = getenv("RC_WIN_WORDS");
-            const int forced = wwv ? std::max(4, atoi(wwv)) : 0;
-            X.win = forced ? 1 : (need > smax ? 1 : 0);
-            X.dsw = forced ? std::min(forced, smax) : std::min(need, smax);
-        }
-        X.defer = e->d_defer.p;
-        X.defer_count = e->d_count.p + 6;
-        X.work = e->d_count.p + 7;
-        X.defer2 = e->d_defer2.p;
-        X.defer2_count = e->d_count.p + 14;
-        X.work2 = e->d_count.p + 15;
-        X.cand_box = e->d_cand_box.p;
-        X.share = e->share ? 1 : 0;
-        X.which = 0;
-        X.dir = 0;
-        X.cand_box2 = e->d_cand_box2.p;
-        X.cand_hsp_r = e->d_cand_hsp_r.p;
-        X.cand_nh_r = e->d_cand_nh_r.p;
-        X.cand_ovf_r = e->d_cand_ovf_r.p;
-        X.defer_r = e->d_defer_r.p;
-        X.defer_r_count = e->d_count.p + 17;
-        X.list2 = e->d_list2.p;
-        X.list2_n = e->d_count.p + 16;
-        X.work3 = e->d_count.p + 18;
-        X.wide0 = e->share ? e->d_wide0.p : nullptr;
-        X.wide1 = e->d_wide1.p;
-        X.wide0_n = e->d_count.p + 20;
-        X.wide1_n = e->d_count.p + 21;
-        {
-            // save overflowing extensions for the 64-lane pass when the last
-            // run had many (C3v: 39 %, C3: 0.002 %): the saving kernel costs
-            // the plain one 7 % (RC_RESUME=1 always, 0 never)
-            const char *rv = getenv("RC_RESUME");
-            const bool on = rv ? atoi(rv) == 1 : e->ovf_frac > 0.02;
-            X.resume = e->res_cap && on ? e->d_resume.p : nullptr;
-            X.res_cap = e->res_cap;
-        }
-        X.work_w0 = e->d_count.p + 22;
-        X.work_w1 = e->d_count.p + 23;
-        X.why = e->d_count.p + 24;   // [24, 27): deferral causes
-        {
-            const char *cv = getenv("RC_ROW_CHUNK");
-            X.chunk = cv ? atoi(cv) : 8;
-            const char *rv = getenv("RC_REUSE");   // 0: extend_kernel redoes every search's first seed
-            X.reuse_first = rv ? atoi(rv) : 1;
-        }
+        ExtParams X = ext_params(e, C);
         if (attempt == 0) {
             HIPCHK(hipEventRecord(e->ev[10], e->st));
-            // sub-band row width of the extension (16 or 32 diagonals); RC_ROW_WIDTH overrides
-            const char *rwv = getenv("RC_ROW_WIDTH");
-            const int rw = rwv ? atoi(rwv) : 32;
-            launch_extend_rows(e->has_amb, db, X, rw, e->st, false);
+            launch_extend_rows(e->has_amb, C.db, X, row_opts(e), e->st);
             HIPCHK(hipGetLastError());
             // only the searches the row kernels left (defer lists) can have
             // more than one HSP, at most MAX_HSP - 1 more each: the overflow
@@ -2064,151 +2167,92 @@ static int align_tile(rc_engine *e, int ti)
             // first run rarely redoes extend_kernel
             unsigned long long dn[3] = {0, 0, 0};
             HIPCHK(hipMemcpyAsync(&dn[0], X.defer_count, sizeof dn[0], hipMemcpyDeviceToHost, e->st));
-            HIPCHK(hipMemcpyAsync(&dn[1], e->d_count.p + 17, sizeof dn[1], hipMemcpyDeviceToHost, e->st));
+            HIPCHK(hipMemcpyAsync(&dn[1], X.defer_r_count, sizeof dn[1], hipMemcpyDeviceToHost, e->st));
             if (X.defer2_count)
                 HIPCHK(hipMemcpyAsync(&dn[2], X.defer2_count, sizeof dn[2], hipMemcpyDeviceToHost, e->st));
             CHK(wait_st(e));
             const uint64_t want = std::min<uint64_t>(2 * (dn[0] + dn[1] + dn[2]), (uint64_t)(MAX_HSP - 1) *
                                                      (dn[0] + dn[1] + dn[2])) + 1024;
-            if (want > e->ovf_cap && !getenv("RC_OVF_CAP0")) {
+            if (want > e->ovf_cap && !e->knobs.ovf_cap0) {
                 e->ovf_cap = want;
                 CHK(e->d_ovf.ensure(e->ovf_cap));
                 X.ovf = e->d_ovf.p;
                 X.ovf_cap = e->ovf_cap;
             }
-            // later-seed rounds: the deferred searches' later seeds on the row
-            // kernels (RC_LATER=0: extend_kernel runs them whole); searches
-            // past RC_LATER_CAP (default 24 M, 12 GB of state and work) run whole
-            const char *lv = getenv("RC_LATER");
-            const uint64_t nsrch = dn[0] + dn[1];
-            if (e->share && X.reuse_first && !(lv && atoi(lv) == 0) && nsrch) {
-                const char *cv = getenv("RC_LATER_CAP");
-                const uint64_t cap = cv ? (uint64_t)std::max(atoll(cv), 1ll) : (24ull << 20);
-                const uint64_t n = std::min(nsrch, cap);
-                CHK(e->d_later.ensure(n * LATER_REC));
-                CHK(e->d_lbox0.ensure(n * BOX_REC));
-                CHK(e->d_lbox1.ensure(n * BOX_REC));
-                CHK(e->d_lvc0.ensure(n));
-                CHK(e->d_lvc1.ensure(n));
-                CHK(e->d_llist0.ensure(n));
-                CHK(e->d_llist1.ensure(n));
-                CHK(e->d_lact0.ensure(n));
-                CHK(e->d_lact1.ensure(n));
-                CHK(e->d_lfull0.ensure(std::max<uint64_t>(dn[0], 1)));
-                CHK(e->d_lfull1.ensure(std::max<uint64_t>(dn[1], 1)));
-                const size_t nc = (size_t)MAX_HSP * LATER_CNT + 4;
-                CHK(e->d_lcnt.ensure(nc));
-                HIPCHK(hipMemsetAsync(e->d_lcnt.p, 0, nc * sizeof(unsigned long long), e->st));
-                lat = LaterParams{};
-                lat.state = e->d_later.p;
-                lat.n_search = nsrch;
-                lat.n0 = dn[0];
-                lat.n_cap = n;
-                lat.defer0 = X.defer;
-                lat.defer1 = X.defer_r;
-                lat.full0 = e->d_lfull0.p;
-                lat.full1 = e->d_lfull1.p;
-                lat.counters = e->d_lcnt.p + (size_t)MAX_HSP * LATER_CNT;
-                lat.full_n = lat.counters + 2;
-                Cand *const vc[2] = {e->d_lvc0.p, e->d_lvc1.p};
-                uint32_t *const ls[2] = {e->d_llist0.p, e->d_llist1.p};
-                int32_t *const bx[2] = {e->d_lbox0.p, e->d_lbox1.p};
-                uint32_t *const ac[2] = {e->d_lact0.p, e->d_lact1.p};
-                launch_later_rounds(e->has_amb, db, X, lat, vc, ls, bx, ac, e->d_lcnt.p, e->st);
-                HIPCHK(hipGetLastError());
-                later_on = true;
-            }
-            if (later_on) {
-                launch_later_finish(X, lat, e->st);
-                X.defer = lat.full0;
-                X.defer_count = lat.full_n;
-                X.defer_r = lat.full1;
-                X.defer_r_count = lat.full_n + 1;
-            }
-            launch_extend_retry(e->has_amb, db, X, e->st);
-        } else {
-            if (later_on) {
-                launch_later_finish(X, lat, e->st);
-                X.defer = lat.full0;
-                X.defer_count = lat.full_n;
-                X.defer_r = lat.full1;
-                X.defer_r_count = lat.full_n + 1;
-            }
+            // (RC_LATER=0: extend_kernel runs the deferred searches whole)
+            if (e->share && X.reuse_first && e->knobs.later && dn[0] + dn[1]) CHK(later_rounds(e, C, X, dn[0], dn[1]));
+        }
+        if (C.later_on) {
+            // (on a retry this counts the MAX_HSP-bound searches again, an
+            // over-count of maxhsp_bound: X.counters is cleared only below)
+            launch_later_finish(X, C.lat, e->st);
+            X.defer = C.lat.full0;
+            X.defer_count = C.lat.full_n;
+            X.defer_r = C.lat.full1;
+            X.defer_r_count = C.lat.full_n + 1;
+        }
+        if (attempt) {
             X.counters = nullptr;   // (the first attempt counted this work)
-            launch_extend_retry(e->has_amb, db, X, e->st);
             e->tm.ext_retries += 1.0;
         }
+        launch_extend_retry(e->has_amb, C.db, X, row_opts(e), e->st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e->ev[11], e->st));
-        unsigned long long ovn = 0, ctr[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, nfull = 0;
-        HIPCHK(hipMemcpyAsync(&nfull, e->d_count.p + 14, sizeof nfull, hipMemcpyDeviceToHost, e->st));
+        unsigned long long ovn = 0, ctr[DC_COUNTERS_END - DC_COUNTERS] = {}, nfull = 0;
+        const auto c = [&](int slot) { return (double)ctr[slot - DC_COUNTERS]; };
+        HIPCHK(hipMemcpyAsync(&nfull, cnt + DC_DEFER2, sizeof nfull, hipMemcpyDeviceToHost, e->st));
         unsigned long long nwide[2] = {0, 0};   // shared searches: candidates the 64-lane passes took
-        HIPCHK(hipMemcpyAsync(nwide, e->d_count.p + 20, sizeof nwide, hipMemcpyDeviceToHost, e->st));
-        unsigned long long why[3] = {0, 0, 0};
-        HIPCHK(hipMemcpyAsync(why, e->d_count.p + 24, sizeof why, hipMemcpyDeviceToHost, e->st));
+        static_assert(DC_WIDE1 == DC_WIDE0 + 1, "read together");
+        HIPCHK(hipMemcpyAsync(nwide, cnt + DC_WIDE0, sizeof nwide, hipMemcpyDeviceToHost, e->st));
+        unsigned long long why[DC_WHY_END - DC_WHY] = {0, 0, 0};
+        HIPCHK(hipMemcpyAsync(why, cnt + DC_WHY, sizeof why, hipMemcpyDeviceToHost, e->st));
         unsigned long long ndr = 0, nl2 = 0;   // shared searches: reverse searches redone whole, second first seeds
-        HIPCHK(hipMemcpyAsync(&ndr, e->d_count.p + 17, sizeof ndr, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(&nl2, e->d_count.p + 16, sizeof nl2, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&ndr, cnt + DC_DEFER_R, sizeof ndr, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&nl2, cnt + DC_LIST2, sizeof nl2, hipMemcpyDeviceToHost, e->st));
         unsigned int status = 0;
-        HIPCHK(hipMemcpyAsync(&ovn, e->d_count.p, sizeof ovn, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(ctr, e->d_count.p + 1, sizeof ctr, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&ovn, cnt + DC_OVF, sizeof ovn, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(ctr, cnt + DC_COUNTERS, sizeof ctr, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
-        if (ctr[8] || ctr[9]) {   // built with RC_ROW_TIMING: wave cycles in transitions / steps
-            unsigned long long tfs[3] = {0, 0, 0};   // fetches, window slides, extension starts (parts of the transitions)
-            HIPCHK(hipMemcpy(tfs, e->d_count.p + 28, sizeof tfs, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemset(e->d_count.p + 28, 0, sizeof tfs));
-            fprintf(stderr, "row kernel wave-cycles: transitions %.4g (fetches %.4g, window slides %.4g, extension "
-                            "starts %.4g) steps %.4g\n",
-                    (double)ctr[8], (double)tfs[0], (double)tfs[1], (double)tfs[2], (double)ctr[9]);
-            // 32-lane rows: steps and candidates within a 16-lane window, its slides (profiles/r06_row16)
-            unsigned long long r16[3] = {0, 0, 0};
-            HIPCHK(hipMemcpy(&r16[0], e->d_count.p + 27, 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(&r16[1], e->d_count.p + 31, 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(&r16[2], e->d_count.p + 32, 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemset(e->d_count.p + 27, 0, 8));
-            HIPCHK(hipMemset(e->d_count.p + 31, 0, 16));
-            fprintf(stderr, "row steps before a live span over 14 diagonals %.4g of %.4g; candidates never over 14: "
-                            "%.4g of %.4g; 16-lane window slides %.4g\n", (double)r16[0], (double)ctr[0],
-                    (double)r16[1], (double)ctr[2], (double)r16[2]);
-            unsigned long long pr[10];
-            HIPCHK(hipMemcpy(pr, e->d_prof.p, sizeof pr, hipMemcpyDeviceToHost));
-            fprintf(stderr, "seed kernel block-cycles: prologue %.4g words: usable %.4g lookup %.4g scan %.4g "
-                            "hits %.4g (loads %.4g pretest %.4g full test %.4g) sort %.4g write %.4g\n",
-                    (double)pr[8], (double)pr[9], (double)pr[0], (double)pr[1], (double)(pr[2] + pr[5] + pr[6] + pr[7]),
-                    (double)pr[5], (double)pr[6], (double)pr[7], (double)pr[3], (double)pr[4]);
-        }
+        if (c(DC_T_TRANS) || c(DC_T_STEPS)) CHK(print_row_timing(e, ctr));   // built with RC_ROW_TIMING
         if (!(status & 1u)) {
-            e->tm.ext_steps += (double)ctr[0];
-            e->tm.ext_calls += (double)ctr[1];
+            e->tm.ext_steps += c(DC_STEPS);
+            e->tm.ext_calls += c(DC_EXTS);
             // candidates the one-wave kernel took (the 64-lane pass's list, or the row kernel's)
-            const char *r64 = getenv("RC_ROW64");
-            e->tm.ext_fullband += (r64 && atoi(r64)) ? (double)nfull : (double)ctr[3];
-            e->ovf_frac = n_cand ? (double)ctr[3] / (double)n_cand : 0.0;
-            e->tm.ext_deferred += (double)ctr[5] + (double)ndr;
+            e->tm.ext_fullband += e->knobs.row64 ? (double)nfull : c(DC_FULLBAND);
+            e->ovf_frac = n_cand ? c(DC_FULLBAND) / (double)n_cand : 0.0;
+            e->tm.ext_deferred += c(DC_DEFER) + (double)ndr;
             e->tm.ext_second += e->share ? (double)nl2 : 0.0;
-            e->tm.band_bound += (double)ctr[7];
-            e->tm.ext_slides += (double)ctr[4];
+            e->tm.band_bound += c(DC_BAND_BOUND);
+            e->tm.ext_slides += c(DC_SLIDES);
             e->tm.ext_wide += (double)(nwide[0] + nwide[1]);
-            e->tm.maxhsp_bound += (double)ctr[10];
+            e->tm.maxhsp_bound += c(DC_MAXHSP);
             e->tm.defer_length += (double)why[0];
             e->tm.defer_gaveup += (double)why[1];
             e->tm.defer_outside += (double)why[2];
-            if (later_on) {   // later-seed rounds: seeds extended on the row kernels, searches run whole
-                std::vector<unsigned long long> lc((size_t)MAX_HSP * LATER_CNT + 4);
+            if (C.later_on) {   // later-seed rounds: seeds extended on the row kernels, searches run whole
+                std::vector<unsigned long long> lc((size_t)MAX_HSP * LATER_CNT + LC_N);
                 HIPCHK(hipMemcpy(lc.data(), e->d_lcnt.p, lc.size() * sizeof(unsigned long long),
                                  hipMemcpyDeviceToHost));
                 for (int r = 0; r < MAX_HSP; r++) e->tm.later_seeds += (double)lc[(size_t)r * LATER_CNT];
-                e->tm.later_whole += (double)lc[(size_t)MAX_HSP * LATER_CNT + 1];
+                e->tm.later_whole += (double)lc[(size_t)MAX_HSP * LATER_CNT + LC_WHOLE];
             }
             break;
         }
         e->ovf_cap = std::max<uint64_t>(e->ovf_cap, ovn * 5 / 4 + 1024);
     }
-    // --- groups: (query gene, subject sample) -> contiguous HSPs, appended ---
-    // Direct groups of every run first, in candidate order; mirrored groups
-    // (spec 5b: the subject->query direction of the same alignments) follow,
-    // each sorted into the order that search emits.
+    return RC_OK;
+}
+
+// Stage 6: (query gene, subject sample) -> contiguous HSPs, appended to the
+// shard's store. Direct groups of every run first, in candidate order;
+// mirrored groups (spec 5b: the subject->query direction of the same
+// alignments) follow, each sorted into the order that search emits. Event ev[4].
+static int group_stage(rc_engine *e, const TileCtx &C)
+{
+    const int N = (int)e->samples.size();
+    const size_t R = C.runs.size();
+    const auto &cnb = C.cnb;
     GroupParams G{};
     G.N = N;
     G.cand_nh = e->d_cand_nh.p;
@@ -2216,12 +2260,12 @@ static int align_tile(rc_engine *e, int ti)
     G.cand_ovf = e->d_cand_ovf.p;
     G.ovf = e->d_ovf.p;
     G.shard_prefix = e->d_shard_prefix.p;
-    G.n_cand = n_cand;
+    G.n_cand = C.n_cand;
     G.cand_cap = e->cand_cap;
     G.tx_gene = e->d_tx_gene.p;
     G.tx_pos = e->d_tx_pos.p;
     G.tx = e->d_tx.p;
-    G.n_genes = n_genes;
+    G.n_genes = (uint32_t)e->gene_sample.size();
     G.grp_off = e->d_grp_off.p;
     G.grp_cnt = e->d_grp_cnt.p;
     auto exscan = [&](const uint32_t *in, uint64_t *out, size_t n) -> int {
@@ -2233,10 +2277,10 @@ static int align_tile(rc_engine *e, int ti)
     };
     auto run_group = [&](size_t r) {
         GroupParams g = G;
-        g.gene_begin = rg0[r];
-        g.gene_end = rg1[r];
-        g.gc_off = e->d_gc_off.p + gcb[r];
-        g.gc_cnt = e->d_gc_cnt.p + gcb[r];
+        g.gene_begin = C.rg0[r];
+        g.gene_end = C.rg1[r];
+        g.gc_off = e->d_gc_off.p + C.gcb[r];
+        g.gc_cnt = e->d_gc_cnt.p + C.gcb[r];
         g.cnt = e->d_gcount.p + cnb[r];
         g.scan = e->d_gscan.p + cnb[r];
         return g;
@@ -2263,7 +2307,7 @@ static int align_tile(rc_engine *e, int ti)
         // query transcript of a pair's a (lower sample) and a subject
         // transcript of its b, so its mirrored group is (gene of b, sample a)
         int a_lo = N, a_hi = 0, b_lo = N, b_hi = 0;
-        for (const auto &pr : TT.pairs) {
+        for (const auto &pr : e->tiles[C.ti].pairs) {
             a_lo = std::min(a_lo, pr.first);
             a_hi = std::max(a_hi, pr.first + 1);
             b_lo = std::min(b_lo, pr.second);
@@ -2276,7 +2320,7 @@ static int align_tile(rc_engine *e, int ti)
         G.mgw = e->sample_gene_begin[b_hi] - e->sample_gene_begin[b_lo];
         const size_t nwin = (size_t)G.mgw * (size_t)G.msn;
         CHK(e->d_mcnt.ensure(nwin + 1));
-        CHK(e->d_mcur.ensure(std::max<uint64_t>(n_cand, 1)));   // per candidate: its slots' start in its group
+        CHK(e->d_mcur.ensure(std::max<uint64_t>(C.n_cand, 1)));   // per candidate: its slots' start in its group
         CHK(e->d_mscan.ensure(nwin + 1));
         G.mcnt = e->d_mcnt.p;
         G.mcur = e->d_mcur.p;
@@ -2305,13 +2349,13 @@ static int align_tile(rc_engine *e, int ti)
     if (mirror) {
         CHK(e->d_mkey.ensure(2 * nm + 2));
         CHK(e->d_mbig.ensure(nm / 33 + 2));
-        HIPCHK(hipMemsetAsync(e->d_count.p + 19, 0, sizeof(unsigned long long), e->st));
+        HIPCHK(hipMemsetAsync(e->d_count.p + DC_MBIG, 0, sizeof(unsigned long long), e->st));
         G.mscan = e->d_mscan.p;
         G.out = e->d_hsp.p;
         G.mbase = base;
         G.mkey = e->d_mkey.p;
         G.mbig = e->d_mbig.p;
-        G.mbig_n = e->d_count.p + 19;
+        G.mbig_n = e->d_count.p + DC_MBIG;
         launch_group(G, 3, e->st);
         launch_group(G, 4, e->st);
     }
@@ -2319,6 +2363,21 @@ static int align_tile(rc_engine *e, int ti)
     HIPCHK(hipEventRecord(e->ev[4], e->st));
     CHK(wait_st(e));
     e->hsp_used = nh;
+    return RC_OK;
+}
+
+// One alignment pass over tile ti: pack, DUST, index, seeds (one launch per
+// run of query samples), extension, and the (query gene, subject sample) HSP
+// groups appended to the shard's store.
+static int align_tile(rc_engine *e, int ti)
+{
+    TileCtx C;
+    C.ti = ti;
+    CHK(index_stage(e, ti));
+    CHK(plan_stage(e, C));
+    CHK(seed_stage(e, C));
+    CHK(extension_stage(e, C));
+    CHK(group_stage(e, C));
     e->tm.pack_ms += ev_ms(e, 0, 1);
     e->tm.index_ms += ev_ms(e, 1, 2);
     if (e->o.dust_level > 0 && !e->external) {
@@ -2462,7 +2521,7 @@ static int do_rbh(rc_engine *e)
     R.edge_off = e->d_off4.p + 3 * (ni + 1);
     R.rows = e->d_rows.p;
     R.edges = e->d_edges.p;
-    if (slot_ovf || getenv("RC_RBH_TWO_PASS"))
+    if (slot_ovf || e->knobs.rbh_two_pass)
         launch_rbh(R, 1, e->st);   // an item had more rows or edges than its slots: full second pass
     else
         launch_rbh_place(R, e->st);
@@ -3011,7 +3070,7 @@ int rc_dust_masks(rc_engine *e, const int32_t *samples, int32_t n, uint64_t *out
     if (own) {
         chunks.push_back(ss);
     } else {
-        const uint64_t cap = tile_cap();
+        const uint64_t cap = e->knobs.tile_bases;
         uint64_t acc = 0;
         for (int s : ss) {
             const uint64_t b = align_up(e->samples[s].nbases);
@@ -3227,7 +3286,7 @@ int rc_trim(rc_engine *e)
     e->d_tile_masked.release(); e->d_ment.release(); e->d_ment2.release(); e->d_mbucket.release();
     e->d_rseeds.release(); e->d_rseed_gene.release(); e->d_rs_key.release(); e->d_rs_idx.release();
     e->d_rs_range.release(); e->d_rctr.release(); e->d_rtmask.release(); e->d_trange.release(); e->d_rtrange.release();
-    e->d_ent.release(); e->d_ent2.release(); e->d_sort_scratch.release(); e->d_gen_tile.release();
+    e->d_ent.release(); e->d_ent2.release(); e->d_sort_scratch.release();
     e->d_sort_status.release(); e->d_bucket.release(); e->d_pos_tx.release(); e->d_sample_pos.release();
     e->d_txstart.release(); e->d_dmask.release(); e->d_dust_scratch.release(); e->d_dust_events.release();
     e->d_prof.release(); e->d_tmp.release(); e->d_seeds.release(); e->d_cands.release();

@@ -485,6 +485,36 @@ def test_tiles_match_one_pass(native, monkeypatch, split, share):
     assert not msgs, "\n".join(msgs[:10])
 
 
+def test_knobs_are_read_when_the_engine_is_created(native, monkeypatch):
+    """The RC_* knobs are read once, in rc_create: variables set after an
+    engine exists do not reach it. An engine created with none set, then
+    RC_SHARE=0, a small RC_TILE_BASES and RC_LATER=0 set before it loads and
+    runs, makes the default run: one tile, the same counts, the same HSPs."""
+    from rna_clique_amd.engine import Engine
+    from rna_clique_amd.simulate import simulate
+    for k in ("RC_SHARE", "RC_TILE_BASES", "RC_LATER"):
+        monkeypatch.delenv(k, raising=False)
+    samples, _ = simulate(3, 60, seed=7, p_iso2=0.2, indel_rate=0.002)
+    n = len(samples)
+    ref = _load(Engine(device=0), samples)   # DUST is on by default
+    ref.run()
+    eng = Engine(device=0)
+    monkeypatch.setenv("RC_SHARE", "0")
+    monkeypatch.setenv("RC_TILE_BASES", str(2 * max(int(s.tx_offsets[-1]) for s in samples)))
+    monkeypatch.setenv("RC_LATER", "0")
+    _load(eng, samples)
+    eng.run()
+    tm, rtm = eng.timings(), ref.timings()   # (both now: the device-memory fields are the process's)
+    assert tm["tiles"] == 1
+    for k in tm:
+        if not k.endswith("_ms"):
+            assert tm[k] == rtm[k], k
+    for q in range(n):
+        for s in range(n):
+            if q != s:
+                assert eng.hsps(q, s).tobytes() == ref.hsps(q, s).tobytes(), (q, s)
+
+
 @pytest.mark.parametrize("shards", [3, 5])
 def test_shards_hold_only_their_samples(native, monkeypatch, shards):
     """Sharded engines given only the sequences of their own pairs' samples

@@ -13,9 +13,10 @@ the compiled geometry (T = OS_TILE, S = OS_SEG, P = BF_PER).
 Not covered here, and left to the end-to-end parity tests: the engine's own
 orchestration (which fill path it picks, tile reuse, the second stream), the
 engine's choice of the bucket `bits` (28 at full size: a 1 GiB table does not
-belong in a test; 16, 17 and 22 run the same kernel), the RC_GEN key
-generation and the RC_SORT=rocprim switch. The look-back epoch tag wraps only
-after 2^31 passes; forcing that is out of scope, and no test touches the epoch.
+belong in a test; 16, 17 and 22 run the same kernel). The sort's key-generator
+first pass is not covered either: the engine no longer uses it. The look-back
+epoch tag wraps only after 2^31 passes; forcing that is out of scope, and no
+test touches the epoch.
 """
 import functools
 

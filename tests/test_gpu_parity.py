@@ -219,8 +219,8 @@ def test_hsp_overflow_retry(native, monkeypatch, share):
 
 
 def test_simulated_parity_large_index(native):
-    """More than 2^20 indexed positions: the onesweep-sorted index (smaller
-    ones take rocPRIM's merge-sort path, sorted on all 64 bits)."""
+    """More than 2^20 indexed positions: an index whose sort (sort.hip's
+    onesweep passes, at every size) runs over many tiles per look-back chain."""
     from rna_clique_amd.simulate import simulate
     samples, _ = simulate(3, 500, seed=41, p_iso2=0.1)
     assert sum(s.seq.size for s in samples) > 2 * (1 << 20)
