@@ -121,7 +121,7 @@ typedef struct rc_timing {
     double ext_steps;         /* greedy X-drop steps executed (wave-level) */
     double ext_calls;         /* greedy extensions (left + right per HSP attempt) */
     double ext_fullband;      /* candidates whose frontier left the row kernel's sub-band (extended whole
-                                 by the one-wave full-band kernel; RC_ROW64=1: by 64-lane rows first) */
+                                 by the one-wave full-band kernel) */
     double ext_deferred;      /* candidates the one-wave kernel took (sub-band exits, seeds outside the
                                  first HSP box, transcripts past the row staging slot) */
     double big_passes;        /* (query gene, subject sample) seed passes run from global memory */

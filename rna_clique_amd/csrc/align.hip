@@ -313,7 +313,7 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
         // canonical pre-test by sequence: a hit whose s bases before it match
         // (inside both transcripts) extends left past p - s: not canonical
         const bool fast = stride <= 32;
-        const bool lpre = !AMB && P.pre_mode == 1 && stride >= 1 && stride < W16;
+        const bool lpre = !AMB && stride >= 1 && stride < W16;
         for (uint32_t ib = 0; ib < n_items; ib += SBLOCK) {
             const uint32_t it = ib + tid;
             uint32_t lo = 0, cnt = 0, info = 0, key = 0;
@@ -1299,24 +1299,16 @@ __global__ __launch_bounds__(EBLOCK, EXT_MIN_WAVES) void extend_kernel(Db db, Ex
 {
     constexpr int NA = AMB ? 4 : 2;
     __shared__ uint64_t stg[EWAVES][NA][SW2];
-    __shared__ unsigned long long sprefix[NSHARD + 1];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i <= NSHARD; i += EBLOCK) sprefix[i] = P.shard_prefix[i];
-    __syncthreads();
     const uint64_t total = db.total;
     const uint64_t nwaves = (uint64_t)gridDim.x * EWAVES;
-    int shard = 0;   // advances monotonically with li
     uint64_t li = (uint64_t)blockIdx.x * EWAVES + wid;
-    // list mode (P.defer set): the candidates extend_dual_kernel deferred
-    const bool list = P.defer != nullptr;
-    const uint64_t n_work = list ? (uint64_t)*P.defer_count : P.n_cand;
+    // the searches the row kernels and first_finish_kernel (or the later-seed
+    // rounds) left: candidate slots P.defer[0, *P.defer_count)
+    const uint64_t n_work = (uint64_t)*P.defer_count;
     // candidate slots are wave-uniform: keep them (and what is loaded through
     // them) in scalar registers
-    auto locate = [&](uint64_t l) -> uint64_t {
-        if (list) return rfl((uint64_t)P.defer[l]);
-        while (shard + 1 < NSHARD && sprefix[shard + 1] <= l) shard++;
-        return rfl((uint64_t)((uint64_t)shard * P.cand_cap + (l - sprefix[shard])));
-    };
+    auto locate = [&](uint64_t l) -> uint64_t { return rfl((uint64_t)P.defer[l]); };
     const Cand *__restrict__ cands = P.cands;
     const TxInfo *__restrict__ txs = db.tx;
     uint32_t steps = 0, exts = 0, ncands = 0, edges = 0, capped = 0;
@@ -1343,7 +1335,7 @@ __global__ __launch_bounds__(EBLOCK, EXT_MIN_WAVES) void extend_kernel(Db db, Ex
         // sub-band overflow): the search starts with that HSP
         const int *fx0 = nullptr;
         int e0 = -1;
-        if (P.share && P.reuse_first) {
+        if (P.share) {
             const bool second = P.dir == 1 && cd.e1 != SEED_NONE;
             const int *fx = (second ? P.cand_box2 : P.cand_box) + ci * BOX_REC;
             if (fx[FX_STATUS] >= 0) {
@@ -1667,9 +1659,6 @@ __device__ __forceinline__ void lds_pair_at(uint32_t a, uint32_t b, uint32_t pa,
 // Matching bases from (pa, pb) forward, at most maxn (>= 0); positions are
 // absolute LDS base positions (lds_win2); masks (AMB) sit `moff` bases
 // further on. Reads bases up to pa + max(maxn, 1) + 47 (WIN_MARGIN).
-#ifndef RC_SLIDE_UNIFORM
-#define RC_SLIDE_UNIFORM 1
-#endif
 template <bool AMB>
 __device__ __forceinline__ int slide_fwd(uint32_t pa, uint32_t pb, int maxn, uint32_t moff)
 {
@@ -1683,7 +1672,6 @@ __device__ __forceinline__ int slide_fwd(uint32_t pa, uint32_t pb, int maxn, uin
         x |= ma | mb;
     }
     int n = x ? (int)(__builtin_ctzll(x) >> 1) : 32;
-#if RC_SLIDE_UNIFORM
     // the loop is wave-uniform (a ballot per round): lanes whose run ended
     // keep their count and stop advancing; no exec-mask bookkeeping per round
     // (the dword addresses follow n: a stopped lane re-reads its last window)
@@ -1704,28 +1692,6 @@ __device__ __forceinline__ int slide_fwd(uint32_t pa, uint32_t pb, int maxn, uin
             go = go && k == 32 && n < maxn;
         } while (__builtin_amdgcn_ballot_w64(go));
     }
-#else
-    if (n == 32 && maxn > 32) {
-        uint32_t a = ((pa + 32u) >> 2) & ~3u, b = ((pb + 32u) >> 2) & ~3u;
-        for (;;) {
-            uint64_t wa, wb;
-            lds_pair_at(a, b, pa, pb, wa, wb);
-            x = wa ^ wb;
-            if (AMB) {
-                lds_pair_at(a + moff / 4u, b + moff / 4u, pa, pb, wa, wb);
-                x |= wa | wb;
-            }
-            if (x) {
-                n += (int)(__builtin_ctzll(x) >> 1);
-                break;
-            }
-            n += 32;
-            if (n >= maxn) break;
-            a += 8u;
-            b += 8u;
-        }
-    }
-#endif
     return min(n, maxn);
 }
 
@@ -2761,7 +2727,7 @@ __device__ __forceinline__ void box_from_fx(const int *fx, int x, int y, int len
 }
 
 // A search the later-seed rounds cannot take: extend_kernel runs it whole
-// (from its first seed's HSP, P.reuse_first)
+// (from its first seed's HSP)
 __device__ __forceinline__ void later_full(const LaterParams &L, int dir, uint64_t ci)
 {
     const unsigned long long i = atomicAdd(&L.full_n[dir], 1ull);
@@ -3259,18 +3225,6 @@ void launch_seed_big(bool amb, const Db &db, const Index &ix, const SeedParams &
         hipLaunchKernelGGL((seed_kernel<false, true, false, false>), dim3(n), dim3(SBLOCK), 0, st, db, ix, P);
 }
 
-void launch_extend(bool amb, const Db &db, const ExtParams &P, hipStream_t st)
-{
-    if (P.n_cand == 0) return;
-    ExtParams W = P;
-    W.defer = nullptr;
-    const uint64_t blocks = 256ull * 8;
-    if (amb)
-        hipLaunchKernelGGL(extend_kernel<true>, dim3((unsigned)blocks), dim3(EBLOCK), 0, st, db, W);
-    else
-        hipLaunchKernelGGL(extend_kernel<false>, dim3((unsigned)blocks), dim3(EBLOCK), 0, st, db, W);
-}
-
 // Row kernel over all candidates, then extend_kernel over the ones it deferred
 // (sub-band overflow, or transcripts longer than the row staging slot). The
 // deferred count stays on the device: the list launch reads it.
@@ -3345,17 +3299,13 @@ static void extend_lists(bool amb, const Db &db, const ExtParams &B, hipStream_t
 // after the HSP overflow buffer overflowed (only extend_kernel writes it; the
 // row kernels' results, first_finish_kernel's and the defer lists stand).
 // The deferred counts stay on the device: the list launches read them.
-void launch_extend_retry(bool amb, const Db &db, const ExtParams &P, const RowOpts &O, hipStream_t st)
+void launch_extend_retry(bool amb, const Db &db, const ExtParams &P, hipStream_t st)
 {
     if (P.n_cand == 0) return;
     ExtParams W = P;
     W.list = nullptr;
     W.list_n = nullptr;
     W.resume = nullptr;
-    if (!P.share && O.row64) {
-        W.defer = P.defer2;
-        W.defer_count = P.defer2_count;
-    }
     extend_lists(amb, db, W, st);
 }
 
@@ -3366,16 +3316,15 @@ void launch_extend_retry(bool amb, const Db &db, const ExtParams &P, const RowOp
 // them. Every count stays on the device: an empty round is a few idle
 // launches. cnt: LATER_CNT zeroed counters per round; the work buffers
 // (vc, list, box) and the active lists alternate between rounds.
-void launch_later_rounds(bool amb, const Db &db, const ExtParams &P, const RowOpts &O, const LaterParams &L0,
+void launch_later_rounds(bool amb, const Db &db, const ExtParams &P, bool rows32_first, const LaterParams &L0,
                          Cand *const vc[2], uint32_t *const list[2], int32_t *const box[2], uint32_t *const act[2],
                          unsigned long long *cnt, hipStream_t st)
 {
     if (!L0.n_search) return;
-    const bool widep = O.wide && P.wide0;
+    const bool widep = P.wide0 != nullptr;
     // later seeds nearly all outgrow the 32-lane window (C3v: 15.3 M of 15.3 M,
-    // profiles/r06_later): straight to 64-lane rows (RC_LATER_ROWS=32: the
-    // 32-lane pass first)
-    const bool rows64 = O.later_rows != 32;
+    // profiles/r06_later): straight to 64-lane rows unless rows32_first
+    // (RC_LATER_ROWS=32: the 32-lane pass first)
     uint64_t g = (L0.n_search + 255) / 256;
     if (g > 8192) g = 8192;
     for (int r = 0; r < MAX_HSP; r++) {
@@ -3400,7 +3349,7 @@ void launch_later_rounds(bool amb, const Db &db, const ExtParams &P, const RowOp
         B.list = list[r & 1];
         B.list_n = c;
         B.work = c + 2;
-        if (rows64) {   // RC_LATER_ROWS=64: straight to the spec's whole band
+        if (!rows32_first) {   // RC_LATER_ROWS=64: straight to the spec's whole band
             B.wide = nullptr;
             B.wide_n = nullptr;
             B.resume = nullptr;
@@ -3437,7 +3386,7 @@ void launch_later_finish(const ExtParams &P, const LaterParams &L, hipStream_t s
 // Row kernels (first seeds) over all candidates, then first_finish_kernel
 // (the caller sizes the HSP overflow buffer from the defer counts, then
 // launch_extend_retry)
-void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, const RowOpts &O, hipStream_t st)
+void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, hipStream_t st)
 {
     if (P.n_cand == 0) return;
     ExtParams W = P;
@@ -3454,11 +3403,10 @@ void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, const RowOpt
         // directed search checked (or listed for extend_kernel) on its own
         // each 32-lane pass is followed by a 64-lane pass (the spec's whole
         // band) over the candidates whose live diagonals outgrew the sliding
-        // sub-band (RC_WIDE=0: they go to the one-wave kernel whole). Most of
-        // them also have seeds outside the first box; extend_kernel starts
-        // those searches from the first seed's HSP (P.reuse_first), so the
-        // 64-lane pass is not redone: C3v 806 vs 875 ms per step.
-        const bool widep = O.wide && P.wide0;
+        // sub-band. Most of them also have seeds outside the first box;
+        // extend_kernel starts those searches from the first seed's HSP, so
+        // the 64-lane pass is not redone: C3v 806 vs 875 ms per step.
+        const bool widep = P.wide0 != nullptr;
         auto wide_pass = [&](const ExtParams &B, uint32_t *lst, unsigned long long *lst_n, unsigned long long *wk) {
             ExtParams V = B;
             V.list = lst;
@@ -3493,25 +3441,7 @@ void launch_extend_rows(bool amb, const Db &db, const ExtParams &P, const RowOpt
     }
     // independent searches / spec 5b: 32-lane rows over every candidate
     launch_rows<32>(amb, db, W, st);
-    // pass 2 (RC_ROW64=1; off by default: at C3 neutral, at C3v 7 % slower,
-    // because 40 % of what it finishes still has seeds outside the first box
-    // and is redone whole by the one-wave kernel): the candidates whose
-    // frontier left the sub-band, on 64-lane rows (the spec's whole band)
-    if (!O.row64) {
-        hipLaunchKernelGGL(first_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, W);
-        return;
-    }
-    ExtParams W2 = W;
-    W2.list = P.defer;
-    W2.list_n = P.defer_count;
-    W2.defer = P.defer2;
-    W2.defer_count = P.defer2_count;
-    W2.work = P.work2;
-    launch_rows<64>(amb, db, W2, st);
-    ExtParams W3 = W;
-    W3.defer = P.defer2;
-    W3.defer_count = P.defer2_count;
-    hipLaunchKernelGGL(first_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, W3);
+    hipLaunchKernelGGL(first_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, W);
 }
 
 void launch_group(const GroupParams &P, int pass, hipStream_t st)

@@ -200,7 +200,6 @@ __host__ __device__ __forceinline__ uint32_t max_iso(int xb)
 struct SeedParams {
     int32_t word;                 // W
     int32_t stride;               // W - 16 + 1
-    int32_t pre_mode;             // canonical pre-test: 1 = previous word's hits (LDS), 0 = sequence windows
     int32_t sym;                  // spec 5b: subjects are higher-numbered samples only
     int32_t share;                // shared searches: query = lower sample, seeds carry SEED_F / SEED_R
     // Shared searches with DUST. The reverse pass (rev = 1; queries = the
@@ -276,8 +275,6 @@ enum DCount {
     DC_COUNTERS_END,    // one past the view the host reads back
     DC_BIG = DC_COUNTERS_END,   // SeedParams::big_n
     DC_BIG_RETRY,       // SeedParams::big_retry_n (follows DC_BIG: cleared together)
-    DC_DEFER2,          // ExtParams::defer2_count
-    DC_WORK2,           // ExtParams::work2
     DC_LIST2,           // list2_n: the seed kernel counts, the extension reads
     DC_DEFER_R,         // ExtParams::defer_r_count
     DC_WORK3,           // ExtParams::work3
@@ -295,10 +292,10 @@ enum DCount {
     DC_T_START,         // ... in extension starts
     DC_T_C16,           // candidates never over 14 diagonals
     DC_T_SL16,          // 16-lane window slides
-    DC_N = 34           // the block's size
+    DC_N = 32           // the block's size
 };
 static_assert(DC_DEFER == DC_COUNTERS + 5 && DC_WORK == DC_COUNTERS + 6, "defer_count and work alias counters[5], [6]");
-static_assert(DC_COUNTERS_END == 12 && DC_WHY == 24 && DC_T_SL16 == 32 && DC_T_SL16 < DC_N, "d_count layout");
+static_assert(DC_COUNTERS_END == 12 && DC_WHY == 22 && DC_T_SL16 == 30 && DC_T_SL16 < DC_N, "d_count layout");
 
 // extend_kernel: one wave per candidate, greedy X-drop, purge, e-value cut.
 struct ExtParams {
@@ -335,9 +332,6 @@ struct ExtParams {
     unsigned long long *defer_count;
     const uint32_t *list;               // row kernel list mode: candidate slots list[0, *list_n)
     const unsigned long long *list_n;
-    uint32_t *defer2;                   // the 64-lane pass's deferrals (-> extend_kernel)
-    unsigned long long *defer2_count;
-    unsigned long long *work2;
     // shared searches (RC_SHARE): one candidate set serves both directed
     // searches of a pair; the reverse search's HSPs go to the _r arrays
     int32_t share;
@@ -358,9 +352,6 @@ struct ExtParams {
     unsigned long long *wide_n;
     uint32_t *wide0, *wide1;            // the e0 pass's and the e1 pass's lists
     unsigned long long *wide0_n, *wide1_n, *work_w0, *work_w1;
-    // extend_kernel (shared searches): start a search from its first seed's
-    // row-kernel result (cand_box / cand_box2) when it has one
-    int32_t reuse_first;
     // shared searches: the state of a 32-lane extension that outgrew its
     // window, saved per wide-list entry (the first res_cap entries), so the
     // 64-lane pass continues it instead of starting over (RES_REC ints each)
@@ -421,14 +412,6 @@ constexpr int HSP_FWD = 2, HSP_REV = 4, HSP_IDX_SHIFT = 3;
 
 // cand_box record: BOX_REC ints per candidate (align.hip FX_*)
 constexpr int BOX_REC = 12;
-
-// Host side only (never passed to a kernel): which row passes the extension
-// launchers of align.hip queue, from the engine's knobs
-struct RowOpts {
-    bool wide;        // RC_WIDE: a 64-lane pass after each 32-lane pass (shared searches)
-    bool row64;       // RC_ROW64: a 64-lane pass over the 32-lane pass's deferrals (independent searches)
-    int later_rows;   // RC_LATER_ROWS: 32 = the later-seed rounds run the 32-lane pass first
-};
 
 
 // group kernels: candidates of each (gene, sample) -> contiguous HSP groups.

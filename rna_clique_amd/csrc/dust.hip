@@ -413,7 +413,7 @@ __global__ void dust_linker_kernel(const TxInfo *__restrict__ tx, uint32_t n_tx,
 // where a transcript starts; the packed arrays are read from position 0)
 void launch_dust(bool amb, uint64_t begin, uint64_t total, const uint64_t *F, const uint64_t *AF, const uint64_t *txstart,
                  const TxInfo *tx, uint32_t n_tx, int level, int window, int linker, uint32_t *scratch,
-                 uint64_t *events, uint32_t scratch_blocks, int max_waves, uint64_t *mask, hipStream_t st)
+                 uint64_t *events, uint32_t scratch_blocks, uint64_t *mask, hipStream_t st)
 {
     if (total <= begin) return;
     const uint64_t nchunk = (total - begin + DCHUNK - 1) / DCHUNK;
@@ -424,8 +424,6 @@ void launch_dust(bool amb, uint64_t begin, uint64_t total, const uint64_t *F, co
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &per_cu, amb ? (const void *)dust_kernel<true> : (const void *)dust_kernel<false>, DW, 0);
-    // max_waves > 0: at most that many waves per SIMD (room for kernels on other streams)
-    if (max_waves > 0) per_cu = std::min(per_cu, 4 * max_waves);
     const uint64_t resident = (uint64_t)std::max(ncu, 1) * (uint64_t)std::max(per_cu, 1);
     const uint64_t g = std::min<uint64_t>(std::min<uint64_t>((nchunk + DW - 1) / DW, scratch_blocks), resident);
     const uint64_t nwords = (total + 31) / 32 + 2;   // readable packed words (the arrays carry padding)

@@ -67,13 +67,12 @@ void launch_seed(bool, const Db &, const Index &, const SeedParams &, hipStream_
 void launch_seed_big(bool, const Db &, const Index &, const SeedParams &, uint32_t, hipStream_t);
 void launch_rs_range(const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
 void launch_dust(bool, uint64_t, uint64_t, const uint64_t *, const uint64_t *, const uint64_t *, const TxInfo *, uint32_t, int,
-                 int, int, uint32_t *, uint64_t *, uint32_t, int, uint64_t *, hipStream_t);
+                 int, int, uint32_t *, uint64_t *, uint32_t, uint64_t *, hipStream_t);
 uint32_t dust_scratch_words(uint32_t);
 uint64_t dust_event_words(uint32_t);
-void launch_extend(bool, const Db &, const ExtParams &, hipStream_t);
-void launch_extend_rows(bool, const Db &, const ExtParams &, const RowOpts &, hipStream_t);
-void launch_extend_retry(bool, const Db &, const ExtParams &, const RowOpts &, hipStream_t);
-void launch_later_rounds(bool, const Db &, const ExtParams &, const RowOpts &, const LaterParams &, Cand *const[2],
+void launch_extend_rows(bool, const Db &, const ExtParams &, hipStream_t);
+void launch_extend_retry(bool, const Db &, const ExtParams &, hipStream_t);
+void launch_later_rounds(bool, const Db &, const ExtParams &, bool, const LaterParams &, Cand *const[2],
                          uint32_t *const[2], int32_t *const[2], uint32_t *const[2], unsigned long long *, hipStream_t);
 void launch_later_finish(const ExtParams &, const LaterParams &, hipStream_t);
 int row_slot_words_max(bool amb);
@@ -292,9 +291,10 @@ struct SampleRec {
 static const uint64_t TILE_ALIGN = 1ull << POS_TX_SHIFT;
 static uint64_t align_up(uint64_t x) { return (x + TILE_ALIGN - 1) & ~(TILE_ALIGN - 1); }
 
-// Tuning knobs and test hooks. The environment is read once, when the engine
-// is created (rc_create); a variable changed later does not reach an engine
-// that exists. One line per variable: name (default) and meaning.
+// Test hooks: every one is set by a GPU test to reach a path that the default
+// takes only at full size. The environment is read once, when the engine is
+// created (rc_create); a variable changed later does not reach an engine that
+// exists. One line per variable: name (default) and meaning.
 struct Knobs {
     bool share;           // RC_SHARE (1): 0 = a pair's two directed searches one after the other
     uint64_t tile_bases;  // RC_TILE_BASES (2^32 - 2^24; at least TILE_ALIGN): a tile's most bases (tests: small tiles)
@@ -306,12 +306,6 @@ struct Knobs {
     uint64_t later_cap;   // RC_LATER_CAP (24 M, at least 1): searches the later-seed rounds hold states for
     bool rbh_two_pass;    // RC_RBH_TWO_PASS (unset; any value sets it): always the full second RBH pass
     int resume;           // RC_RESUME (unset = -1: by the last run's overflows): 1 = always save 32-lane states, 0 = never
-    bool wide;            // RC_WIDE (1): 0 = what outgrows the 32-lane window goes to the one-wave kernel whole
-    bool row64;           // RC_ROW64 (0): 1 = independent searches: a 64-lane pass over the 32-lane pass's deferrals
-    int seed_pre;         // RC_SEED_PRE (1): the seed kernel's SeedParams::pre_mode; 1 = hit-list pre-test
-    int reuse;            // RC_REUSE (1): 0 = extend_kernel redoes every search's first seed
-    int index_bits_max;   // RC_INDEX_BITS_MAX (28, clamped to [16, 30]): most bucket-table bits of a seed index
-    int dust_waves;       // RC_DUST_WAVES (0 = every resident wave): DUST waves per SIMD
 };
 
 static Knobs read_knobs()
@@ -330,12 +324,6 @@ static Knobs read_knobs()
     k.later_cap = env("RC_LATER_CAP") ? (uint64_t)std::max(atoll(env("RC_LATER_CAP")), 1ll) : (24ull << 20);
     k.rbh_two_pass = env("RC_RBH_TWO_PASS") != nullptr;
     k.resume = num("RC_RESUME", -1);
-    k.wide = num("RC_WIDE", 1) != 0;
-    k.row64 = num("RC_ROW64", 0) != 0;
-    k.seed_pre = num("RC_SEED_PRE", 1);
-    k.reuse = num("RC_REUSE", 1);
-    k.index_bits_max = std::max(16, std::min(30, num("RC_INDEX_BITS_MAX", 28)));
-    k.dust_waves = num("RC_DUST_WAVES", 0);
     return k;
 }
 
@@ -482,7 +470,7 @@ struct rc_engine {
     bool share = false;
     DBuf<DRow> d_rows_tmp;
     DBuf<DEdge> d_edges_tmp;
-    DBuf<uint32_t> d_cand_ovf, d_gc_off, d_gc_cnt, d_gcount, d_defer, d_defer2;
+    DBuf<uint32_t> d_cand_ovf, d_gc_off, d_gc_cnt, d_gcount, d_defer;
     DBuf<uint64_t> d_gscan, d_mscan, d_mkey, d_tmask, d_mbig;
     DBuf<uint32_t> d_mcnt, d_mcur, d_tx_pos, d_iso_pre, d_iso_list, d_iso_list_r;
     DBuf<unsigned long long> d_shard_cnt, d_shard_prefix;
@@ -1211,9 +1199,10 @@ static int load_tile(rc_engine *e, int ti)
 
 // Sort index entries ent[0, npos) on key bits [bb, 64) into ent2 and build the
 // bucket table over the top k-mer bits: about one bucket per entry (times
-// 2^extra), at most 2^28 (RC_INDEX_BITS_MAX; 28 measured best at C3 -- a 1 GiB
-// table instead of 4 GiB, same seed-kernel time). counted: the fill left the
+// 2^extra), at most 2^INDEX_BITS_MAX (28 measured best at C3 -- a 1 GiB table
+// instead of 4 GiB, same seed-kernel time). counted: the fill left the
 // sort's segment histograms in d_sort_scratch.
+constexpr int INDEX_BITS_MAX = 28;
 static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, uint64_t npos, unsigned bb, int extra,
                       DBuf<uint32_t> &bucket, int &bits_out, bool counted = false)
 {
@@ -1238,7 +1227,7 @@ static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, u
         }
     }
     int bits = 16;
-    while (bits < e->knobs.index_bits_max && (1ull << bits) < (npos << extra)) bits++;
+    while (bits < INDEX_BITS_MAX && (1ull << bits) < (npos << extra)) bits++;
     bits_out = bits;
     CHK(bucket.ensure((1ull << bits) + 1));
     launch_bucket_fill(ent2.p, npos, bits, bucket.p, e->st);
@@ -1475,7 +1464,6 @@ static int reverse_pass(rc_engine *e, int ti, const Db &db, const Index &ixm, ui
             S.iso_n = ioff[ri + 1] - ioff[ri];
             S.word = e->o.word_size;
             S.stride = e->o.word_size - W16 + 1;
-            S.pre_mode = e->knobs.seed_pre;
             S.rev = 1;
             S.tx_pos = e->d_tx_pos.p;
             S.iso_pre_g = e->d_iso_pre.p;
@@ -1609,7 +1597,6 @@ static int dust_samples(rc_engine *e, const std::vector<int> &ss, hipStream_t st
     const uint32_t dblocks = 256 * 28;   // at least the resident waves of the chunk kernel (<= 7 per SIMD): their scratch
     CHK(e->d_dust_scratch.ensure(dust_scratch_words(dblocks)));
     CHK(e->d_dust_events.ensure(dust_event_words(dblocks)));
-    const int dwaves = e->knobs.dust_waves;   // 0: every resident wave (measured best; 1-3 starve DUST)
     int f = -1, l = -1;
     auto flush = [&]() {
         if (f >= 0) {
@@ -1617,8 +1604,8 @@ static int dust_samples(rc_engine *e, const std::vector<int> &ss, hipStream_t st
             launch_dust(e->has_amb, e->tile_pos[f], e->tile_pos[l] + align_up(e->samples[l].nbases),
                         e->d_F.p + FRONT_PAD, e->has_amb ? e->d_AF.p + FRONT_PAD : nullptr, e->d_txstart.p + 1,
                         e->d_tile_tx.p + tx0, e->tile_tx_first[l + 1] - tx0, e->o.dust_level, e->o.dust_window,
-                        e->o.dust_linker, e->d_dust_scratch.p, e->d_dust_events.p, dblocks, dwaves,
-                        e->d_dmask.p + 1, st);
+                        e->o.dust_linker, e->d_dust_scratch.p, e->d_dust_events.p, dblocks, e->d_dmask.p + 1,
+                        st);
         }
         f = l = -1;
     };
@@ -1651,8 +1638,6 @@ struct TileCtx {
     bool later_on = false;                   // the later-seed rounds ran: lat holds their parameters
     LaterParams lat{};
 };
-
-static RowOpts row_opts(const rc_engine *e) { return RowOpts{e->knobs.wide, e->knobs.row64, e->knobs.later_rows}; }
 
 // Stage 1: the tile's tables and packed copy, DUST masks (on the second
 // stream), the seed index (built, or the previous tile's) and, for shared
@@ -1872,7 +1857,6 @@ static int seed_stage(rc_engine *e, TileCtx &C)
         SeedParams S0{};
         S0.word = e->o.word_size;
         S0.stride = e->o.word_size - W16 + 1;
-        S0.pre_mode = e->knobs.seed_pre;
         S0.sym = e->o.symmetric;
         S0.share = e->share ? 1 : 0;
         S0.tx_pos = e->d_tx_pos.p;
@@ -1904,7 +1888,7 @@ static int seed_stage(rc_engine *e, TileCtx &C)
         n_big = 0;
         for (size_t r = 0; r < R && !again; r++) {
             // (DC_BIG and DC_BIG_RETRY)
-            HIPCHK(hipMemsetAsync(big_n, 0, (DC_DEFER2 - DC_BIG) * sizeof(unsigned long long), e->st));
+            HIPCHK(hipMemsetAsync(big_n, 0, (DC_LIST2 - DC_BIG) * sizeof(unsigned long long), e->st));
             SeedParams S = S0;
             S.gene_begin = C.rg0[r];
             S.gene_end = C.rg1[r];
@@ -1996,9 +1980,6 @@ static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
     X.defer = e->d_defer.p;
     X.defer_count = cnt + DC_DEFER;
     X.work = cnt + DC_WORK;
-    X.defer2 = e->d_defer2.p;
-    X.defer2_count = cnt + DC_DEFER2;
-    X.work2 = cnt + DC_WORK2;
     X.cand_box = e->d_cand_box.p;
     X.share = e->share ? 1 : 0;
     X.which = 0;
@@ -2028,7 +2009,6 @@ static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
     X.work_w1 = cnt + DC_WORK_W1;
     X.why = cnt + DC_WHY;
     X.chunk = 8;   // candidates per work grab of the row kernels
-    X.reuse_first = e->knobs.reuse;
     return X;
 }
 
@@ -2068,7 +2048,7 @@ static int later_rounds(rc_engine *e, TileCtx &C, const ExtParams &X, uint64_t d
     uint32_t *const ls[2] = {e->d_llist0.p, e->d_llist1.p};
     int32_t *const bx[2] = {e->d_lbox0.p, e->d_lbox1.p};
     uint32_t *const ac[2] = {e->d_lact0.p, e->d_lact1.p};
-    launch_later_rounds(e->has_amb, C.db, X, row_opts(e), lat, vc, ls, bx, ac, e->d_lcnt.p, e->st);
+    launch_later_rounds(e->has_amb, C.db, X, e->knobs.later_rows == 32, lat, vc, ls, bx, ac, e->d_lcnt.p, e->st);
     HIPCHK(hipGetLastError());
     C.later_on = true;
     return RC_OK;
@@ -2135,7 +2115,6 @@ static int extension_stage(rc_engine *e, TileCtx &C)
         if (e->res_cap) CHK(e->d_resume.ensure((size_t)e->res_cap * RES_REC));
     }
     CHK(e->d_defer.ensure(std::max<uint64_t>(n_cand, 1)));
-    CHK(e->d_defer2.ensure(std::max<uint64_t>(n_cand, 1)));
     // later-seed rounds: their parameters (C.lat) once they ran (a retry
     // finishes the searches again from the states, and extend_kernel takes the
     // lists of the searches they left whole instead of first_finish_kernel's)
@@ -2147,7 +2126,6 @@ static int extension_stage(rc_engine *e, TileCtx &C)
             // every slot the extension counts in; the seed stage's (DC_BIG,
             // DC_BIG_RETRY, DC_LIST2) and the groups' (DC_MBIG) stand
             HIPCHK(hipMemsetAsync(cnt + DC_OVF, 0, (DC_COUNTERS_END - DC_OVF) * sizeof(unsigned long long), e->st));
-            HIPCHK(hipMemsetAsync(cnt + DC_DEFER2, 0, (DC_LIST2 - DC_DEFER2) * sizeof(unsigned long long), e->st));
             HIPCHK(hipMemsetAsync(cnt + DC_DEFER_R, 0, (DC_MBIG - DC_DEFER_R) * sizeof(unsigned long long), e->st));
             HIPCHK(hipMemsetAsync(cnt + DC_WIDE0, 0, (DC_WHY_END - DC_WIDE0) * sizeof(unsigned long long), e->st));
         } else {
@@ -2159,20 +2137,18 @@ static int extension_stage(rc_engine *e, TileCtx &C)
         ExtParams X = ext_params(e, C);
         if (attempt == 0) {
             HIPCHK(hipEventRecord(e->ev[10], e->st));
-            launch_extend_rows(e->has_amb, C.db, X, row_opts(e), e->st);
+            launch_extend_rows(e->has_amb, C.db, X, e->st);
             HIPCHK(hipGetLastError());
             // only the searches the row kernels left (defer lists) can have
             // more than one HSP, at most MAX_HSP - 1 more each: the overflow
             // buffer at twice their count (about 1.1 more each at C3v), so a
             // first run rarely redoes extend_kernel
-            unsigned long long dn[3] = {0, 0, 0};
+            unsigned long long dn[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(&dn[0], X.defer_count, sizeof dn[0], hipMemcpyDeviceToHost, e->st));
             HIPCHK(hipMemcpyAsync(&dn[1], X.defer_r_count, sizeof dn[1], hipMemcpyDeviceToHost, e->st));
-            if (X.defer2_count)
-                HIPCHK(hipMemcpyAsync(&dn[2], X.defer2_count, sizeof dn[2], hipMemcpyDeviceToHost, e->st));
             CHK(wait_st(e));
-            const uint64_t want = std::min<uint64_t>(2 * (dn[0] + dn[1] + dn[2]), (uint64_t)(MAX_HSP - 1) *
-                                                     (dn[0] + dn[1] + dn[2])) + 1024;
+            const uint64_t nd = dn[0] + dn[1];
+            const uint64_t want = std::min<uint64_t>(2 * nd, (uint64_t)(MAX_HSP - 1) * nd) + 1024;
             if (want > e->ovf_cap && !e->knobs.ovf_cap0) {
                 e->ovf_cap = want;
                 CHK(e->d_ovf.ensure(e->ovf_cap));
@@ -2180,7 +2156,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
                 X.ovf_cap = e->ovf_cap;
             }
             // (RC_LATER=0: extend_kernel runs the deferred searches whole)
-            if (e->share && X.reuse_first && e->knobs.later && dn[0] + dn[1]) CHK(later_rounds(e, C, X, dn[0], dn[1]));
+            if (e->share && e->knobs.later && dn[0] + dn[1]) CHK(later_rounds(e, C, X, dn[0], dn[1]));
         }
         if (C.later_on) {
             // (on a retry this counts the MAX_HSP-bound searches again, an
@@ -2195,12 +2171,11 @@ static int extension_stage(rc_engine *e, TileCtx &C)
             X.counters = nullptr;   // (the first attempt counted this work)
             e->tm.ext_retries += 1.0;
         }
-        launch_extend_retry(e->has_amb, C.db, X, row_opts(e), e->st);
+        launch_extend_retry(e->has_amb, C.db, X, e->st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e->ev[11], e->st));
-        unsigned long long ovn = 0, ctr[DC_COUNTERS_END - DC_COUNTERS] = {}, nfull = 0;
+        unsigned long long ovn = 0, ctr[DC_COUNTERS_END - DC_COUNTERS] = {};
         const auto c = [&](int slot) { return (double)ctr[slot - DC_COUNTERS]; };
-        HIPCHK(hipMemcpyAsync(&nfull, cnt + DC_DEFER2, sizeof nfull, hipMemcpyDeviceToHost, e->st));
         unsigned long long nwide[2] = {0, 0};   // shared searches: candidates the 64-lane passes took
         static_assert(DC_WIDE1 == DC_WIDE0 + 1, "read together");
         HIPCHK(hipMemcpyAsync(nwide, cnt + DC_WIDE0, sizeof nwide, hipMemcpyDeviceToHost, e->st));
@@ -2218,8 +2193,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
         if (!(status & 1u)) {
             e->tm.ext_steps += c(DC_STEPS);
             e->tm.ext_calls += c(DC_EXTS);
-            // candidates the one-wave kernel took (the 64-lane pass's list, or the row kernel's)
-            e->tm.ext_fullband += e->knobs.row64 ? (double)nfull : c(DC_FULLBAND);
+            e->tm.ext_fullband += c(DC_FULLBAND);
             e->ovf_frac = n_cand ? c(DC_FULLBAND) / (double)n_cand : 0.0;
             e->tm.ext_deferred += c(DC_DEFER) + (double)ndr;
             e->tm.ext_second += e->share ? (double)nl2 : 0.0;
@@ -3297,7 +3271,7 @@ int rc_trim(rc_engine *e)
     e->d_llist0.release(); e->d_llist1.release(); e->d_lact0.release(); e->d_lact1.release(); e->d_lcnt.release();
     e->d_lfull0.release(); e->d_lfull1.release();
     e->d_rows_tmp.release(); e->d_edges_tmp.release(); e->d_cand_ovf.release(); e->d_gc_off.release();
-    e->d_gc_cnt.release(); e->d_gcount.release(); e->d_defer.release(); e->d_defer2.release(); e->d_gscan.release();
+    e->d_gc_cnt.release(); e->d_gcount.release(); e->d_defer.release(); e->d_gscan.release();
     e->d_mscan.release(); e->d_mkey.release(); e->d_tmask.release(); e->d_mbig.release(); e->d_mcnt.release();
     e->d_mcur.release(); e->d_big_out.release(); e->d_big_list.release(); e->d_big_retry.release();
     e->d_big_seeds.release(); e->d_big_seg.release(); e->d_big_segT.release(); e->d_cnt4.release();

@@ -8,6 +8,7 @@ Post-alignment: oracle/post_oracle.py, itself pinned to the reference by
 tests/golden/post_alignment.json -- and the engine is also run directly on
 those golden HSP tables (external-alignment mode).
 """
+import functools
 import json
 import os
 
@@ -269,15 +270,10 @@ def test_simulated_parity_long_and_gappy(native, lens, indel):
     assert tm["defer_length"] == 0 and tm["defer_gaveup"] == 0
 
 
-@pytest.mark.parametrize("words,share,amb", [(4, 1, False), (9, 1, False), (5, 0, False), (6, 1, True)])
-def test_windowed_staging_exact(native, monkeypatch, words, share, amb):
-    """The row kernels' windowed staging (windows of `words` u64 words, 80 to
-    240 bases past the read margin: a refill every few steps) gives every HSP,
-    table and distance of the whole-transcript staging: indels (wide live
-    bands, the 64-lane pass resuming 32-lane extensions), minus strands,
-    isoforms, poly-A tails, ambiguous bases; shared and one-by-one searches."""
-    monkeypatch.setenv("RC_WIN_WORDS", str(words))
-    monkeypatch.setenv("RC_SHARE", str(share))
+@functools.lru_cache(maxsize=None)
+def _windowed_corpus(amb):
+    """Indels (wide live bands), minus strands, isoforms, poly-A tails; amb:
+    with ambiguous bases. Shared between tests: read only."""
     from rna_clique_amd.simulate import simulate
     samples, _ = simulate(4, 100, seed=23, p_iso2=0.2, indel_rate=0.004, p_revcomp=0.5, polya=(0.3, 10, 40),
                           len_loc=600, len_n=2000, len_p=0.5)
@@ -288,11 +284,62 @@ def test_windowed_staging_exact(native, monkeypatch, words, share, amb):
             pos = np.flatnonzero(rng.random(seq.size) < 0.003)
             seq[pos] = ord("N")
             sm.seq = seq
+    return samples
+
+
+@pytest.mark.parametrize("words,share,amb", [(4, 1, False), (9, 1, False), (5, 0, False), (6, 1, True)])
+def test_windowed_staging_exact(native, monkeypatch, words, share, amb):
+    """The row kernels' windowed staging (windows of `words` u64 words, 80 to
+    240 bases past the read margin: a refill every few steps) gives every HSP,
+    table and distance of the whole-transcript staging: indels (wide live
+    bands, the 64-lane pass after the 32-lane one), minus strands, isoforms,
+    poly-A tails, ambiguous bases; shared and one-by-one searches. A fresh
+    engine saves no 32-lane state, so the 64-lane pass starts these extensions
+    over; test_resume_saved_extensions_exact covers the pass that resumes."""
+    monkeypatch.setenv("RC_WIN_WORDS", str(words))
+    monkeypatch.setenv("RC_SHARE", str(share))
+    samples = _windowed_corpus(amb)
     eng = _run_sim(samples)
     msgs, summary = full_check(eng, samples)
     assert not msgs, "\n".join(msgs[:10])
     tm = eng.timings()
     assert summary["hsps"] > 0 and tm["defer_length"] == 0 and (tm["ext_wide"] > 0 or not share)
+
+
+@functools.lru_cache(maxsize=None)
+def _resume0_stats(amb):
+    """Graph statistics of _windowed_corpus(amb) with no 32-lane state saved
+    (RC_RESUME=0: the 64-lane pass starts every extension over)."""
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("RC_SHARE", "1")
+        mp.setenv("RC_RESUME", "0")
+        mp.delenv("RC_WIN_WORDS", raising=False)
+        with _run_sim(_windowed_corpus(amb)) as eng:
+            return eng.stats()
+
+
+@pytest.mark.parametrize("words,amb", [(None, False), (5, False), (6, True)])
+def test_resume_saved_extensions_exact(native, monkeypatch, words, amb):
+    """RC_RESUME=1 on a fresh engine: the 32-lane pass saves the state of every
+    extension that outgrows its window and the 64-lane pass continues from it
+    (by default only a run after one with many overflows does). The plain,
+    windowed and ambiguous-base saving row kernels: whole-transcript staging,
+    windows of 5 words, windows of 6 words with N bases. Every HSP, table and
+    distance of the oracle, and the graph statistics of a run that saves
+    nothing (RC_RESUME=0)."""
+    monkeypatch.setenv("RC_SHARE", "1")
+    monkeypatch.setenv("RC_RESUME", "1")
+    if words:
+        monkeypatch.setenv("RC_WIN_WORDS", str(words))
+    else:
+        monkeypatch.delenv("RC_WIN_WORDS", raising=False)
+    samples = _windowed_corpus(amb)
+    eng = _run_sim(samples)
+    msgs, summary = full_check(eng, samples)
+    assert not msgs, "\n".join(msgs[:10])
+    tm = eng.timings()
+    assert summary["hsps"] > 0 and tm["ext_wide"] > 0
+    assert eng.stats() == _resume0_stats(amb)
 
 
 @pytest.mark.parametrize("later,rows,cap,words", [("1", "64", None, None), ("1", "32", None, None),
@@ -325,6 +372,26 @@ def test_later_seed_rounds_exact(native, monkeypatch, later, rows, cap, words):
         assert (tm["later_whole"] > 0) == (cap is not None)
     else:
         assert tm["later_seeds"] == 0
+
+
+def test_later_seed_rounds_resume_exact(native, monkeypatch):
+    """The later-seed rounds with 32-lane rows first (RC_LATER_ROWS=32) and
+    RC_RESUME=1: each round's 32-lane pass saves the extensions that outgrow
+    its window for the round's 64-lane pass. The corpus of
+    test_later_seed_rounds_exact. (ext_wide counts the first seeds' 64-lane
+    passes; the rounds keep their wide lists in their own counters.)"""
+    monkeypatch.setenv("RC_SHARE", "1")
+    monkeypatch.setenv("RC_LATER", "1")
+    monkeypatch.setenv("RC_LATER_ROWS", "32")
+    monkeypatch.setenv("RC_RESUME", "1")
+    from rna_clique_amd.simulate import simulate
+    samples, _ = simulate(4, 100, seed=29, p_iso2=0.2, indel_rate=0.012, p_revcomp=0.5, polya=(0.3, 10, 40),
+                          len_loc=600, len_n=2000, len_p=0.5)
+    eng = _run_sim(samples)
+    msgs, summary = full_check(eng, samples)
+    assert not msgs, "\n".join(msgs[:10])
+    tm = eng.timings()
+    assert summary["hsps"] > 0 and tm["later_seeds"] > 0 and tm["ext_wide"] > 0
 
 
 @pytest.mark.parametrize("top_matches,keep_all,two_pass", [(1, True, False), (1, False, False), (2, True, False),
