@@ -14,7 +14,18 @@ Plain-Python restatement of the reference, one function per reference step:
   distance_matrix           similarity_computer.py:216-345
 
 Pinned against tests/golden/post_alignment.json (captured from the reference
-itself by tests/golden/make_golden.py).
+itself by tests/golden/make_golden.py: up to 6 samples, groups of at most 6
+HSPs, one HSP per transcript pair, top_matches 1 and 2) and against
+tests/golden/post_alignment_ties.json (the same capture on the tie-heavy cases
+of tests/post_cases.py: 2-4 samples, 400-480 HSPs drawn from five bit scores,
+groups of up to 16 HSPs, top_matches 1, 3 and 5, and crafted tables for a
+maximum tied across subject genes, keep_all within 2 rows and 1 edge an item,
+and duplicates at the nlargest threshold).
+
+Tie order: rows with equal bit scores stay in frame order in every nlargest
+step. The reference does the same except in groups of at most n rows on a
+machine where numpy's quicksort is one of its SIMD sorting networks (quirk Q2,
+DESIGN.md section 2); the second file is recorded with those disabled.
 
 A row is a dict with the 20 gene-matches-table columns (docs/formats.md:231-252)
 plus "label" (the pandas index label the reference keeps, A7).

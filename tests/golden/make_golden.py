@@ -18,6 +18,29 @@ reference's own code (stub-imported by ref_harness.py):
 
 and writes inputs + outputs to tests/golden/post_alignment.json. The fixture is
 data (inputs and expected outputs); no reference source is copied.
+
+A second file, tests/golden/post_alignment_ties.json, holds the reference's
+output on the tie-heavy and crafted cases of tests/post_cases.py
+(`fixture_cases()`): groups of up to 16 HSPs with few distinct scores,
+top_matches 1, 3 and 5, several rows and edges per item, duplicates at the
+nlargest threshold. Each case's hits and transcripts are stored once, with one
+`expected` per (top_matches, keep_all) setting.
+
+    python tests/golden/make_golden.py --only ties   # the second file alone
+    python tests/golden/make_golden.py --only base   # post_alignment.json alone
+
+Tie order (reference quirk Q2). For a group of at most `n` rows pandas'
+nlargest(n) falls back to Series.sort_values, i.e. numpy's default quicksort.
+Up to 16 elements that is an insertion sort, which keeps tied rows in frame
+order -- unless numpy dispatches to its AVX2 / AVX-512 sorting networks, which
+do not: there the order of tied rows (hence the labels after reset_index, and
+the row that keep="first" picks) depends on the CPU the reference runs on.
+The oracle, post_fast and the engine follow the portable rule (ties in frame
+order, the rule of nlargest's own n < len(group) branch), so this script
+records the reference with numpy's SIMD sorts switched off
+(NPY_DISABLE_CPU_FEATURES, set below before numpy is imported) and, for the
+second file, lists under "reference_quirks" the (case, setting) whose tables
+come out differently with this machine's SIMD sort.
 """
 from __future__ import annotations
 
@@ -27,10 +50,17 @@ import math
 import os
 import sys
 
-import numpy as np
+PORTABLE_SORT = "AVX2 AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL"
+if "--simd-sort" not in sys.argv:
+    assert "numpy" not in sys.modules, "run as a script: numpy must not be imported yet"
+    os.environ["NPY_DISABLE_CPU_FEATURES"] = PORTABLE_SORT
+
+import numpy as np  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))   # oracle.post_oracle (transcript id parsing)
 import ref_harness  # noqa: E402
 
 HSP_COLUMNS = ["qseqid", "sseqid", "pident", "length", "mismatch", "gapopen",
@@ -261,5 +291,80 @@ def main():
               "valid", len(e.get("valid", [])))
 
 
+def _tables_digest(res):
+    import hashlib
+    return hashlib.sha256(json.dumps(res["tables"], sort_keys=True).encode()).hexdigest()
+
+
+def simd_digests():
+    """--simd-sort: the tables' digests per (case, setting) with numpy's own
+    sort dispatch (no NPY_DISABLE_CPU_FEATURES), printed as JSON."""
+    import post_cases
+    out = {}
+    for case in post_cases.fixture_cases():
+        for top_matches, keep_all in post_cases.FIXTURE_SETTINGS:
+            res = run_reference(case.samples, case.hits, top_matches, keep_all)
+            out[f"{case.name} {top_matches}-{keep_all}"] = _tables_digest(res)
+    return out
+
+
+def main_ties():
+    import subprocess
+    import post_cases
+    env = {k: v for k, v in os.environ.items() if k != "NPY_DISABLE_CPU_FEATURES"}
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--simd-sort"], env=env, check=True,
+                           stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+    simd = json.loads(child.stdout.strip().splitlines()[-1])
+    differs = []
+    fixtures = []
+    for case in post_cases.fixture_cases():
+        assert all(case.hits.values()), "no empty searches in captured cases"
+        expected = {}
+        for top_matches, keep_all in post_cases.FIXTURE_SETTINGS:
+            res = run_reference(case.samples, case.hits, top_matches, keep_all)
+            assert not any(k != "matrix" for k in res["errors"]), (case.name, res["errors"])
+            expected[f"{top_matches}-{keep_all}"] = json.loads(json.dumps(res))
+            if simd[f"{case.name} {top_matches}-{keep_all}"] != _tables_digest(res):
+                differs.append(f"{case.name} {top_matches}-{keep_all}")
+        packed = json.loads(json.dumps(post_cases.pack_fixture(case, expected)))
+        # the stored form loses nothing: it unpacks to the inputs and to what the reference returned
+        back = post_cases.unpack_fixture(packed)
+        assert back["expected"] == expected and back["hits"] == case.hits and back["transcripts"] == case.transcripts
+        fixtures.append(packed)
+    assert ["label"] + TABLE_COLUMNS == post_cases.TABLE_COLUMNS and HSP_COLUMNS == post_cases.HSP_COLUMNS
+    path = os.path.join(HERE, "post_alignment_ties.json")
+    head = {"generator": "tests/golden/make_golden.py --only ties (cases and stored form: tests/post_cases.py)",
+            "reference": "actapia/rna_clique (stub-imported post-alignment modules)",
+            "id_format": post_cases.ID_FORMAT,
+            "hit_columns": post_cases.HIT_STORED,
+            "table_row": ["label", "reverse", "index of the HSP in its search"],
+            "settings": [list(s) for s in post_cases.FIXTURE_SETTINGS],
+            "reference_quirks": {"Q2_unstable_tie_order": {
+                "recorded_with": "NPY_DISABLE_CPU_FEATURES=" + PORTABLE_SORT,
+                "tables_differ_with_simd_sort": differs}}}
+    with open(path, "w") as f:
+        f.write(json.dumps(head, separators=(",", ":"))[:-1] + ',"fixtures":[\n')
+        f.write(",\n".join(json.dumps(fx, separators=(",", ":")) for fx in fixtures) + "\n]}\n")
+    print(f"wrote {path}: {len(fixtures)} fixtures, {os.path.getsize(path) / 1e3:.0f} kB")
+    print("tables that differ with this machine's SIMD sort (Q2):", differs)
+    for fx in fixtures:
+        for key, e in fx["expected"].items():
+            print(fx["name"], key, "hsps", sum(len(v) for v in fx["hits"].values()), "table rows",
+                  sum(len(v) for v in e["tables"].values()), "q1ok", e["mapping_from_dfs_ok"], "valid", len(e["valid"]))
+
+
 if __name__ == "__main__":
-    main()
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--only", choices=["base", "ties"], help="write one of the two files (default: both)")
+    ap.add_argument("--simd-sort", action="store_true", help="print the ties cases' table digests under numpy's "
+                    "own sort dispatch (used by the ties capture itself)")
+    args = ap.parse_args()
+    if args.simd_sort:
+        print(json.dumps(simd_digests()))
+        sys.exit(0)
+    only = args.only
+    if only != "ties":
+        main()
+    if only != "base":
+        main_ties()
