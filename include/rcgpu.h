@@ -154,6 +154,9 @@ typedef struct rc_timing {
                                  later-seed rounds, one seed per search per round) */
     double later_whole;       /* deferred searches extend_kernel ran whole (a row kernel gave a seed up,
                                  or past the rounds' capacity, RC_LATER_CAP) */
+    double index_fb_ranges;   /* main-index ranges too large for the range-local sort, sorted by the 8-bit
+                                 passes instead (every range of an index whose list of them overflowed) */
+    double index_fb_keys;     /* ... and the index entries in them */
 } rc_timing;
 
 void rc_default_opts(rc_opts *opts);

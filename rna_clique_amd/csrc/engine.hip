@@ -52,6 +52,17 @@ bool os_sort_keys(uint64_t *keys, uint64_t *alt, uint64_t n, int bb, uint32_t *s
                   uint32_t *gen_tile);
 void os_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
                   uint64_t n, uint32_t *scratch, hipStream_t st);
+int os_index_gbits(uint64_t n, int bits, uint32_t cap);
+uint64_t os_index_status_words(uint64_t n);
+uint64_t os_index_scratch_words(uint64_t n);
+uint64_t os_index_offset_words(int G);
+uint64_t os_index_list_words();
+void os_index_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
+                        uint64_t n, int G, uint32_t *scratch, hipStream_t st);
+int os_index_sort(uint64_t *keys, uint64_t *alt, uint64_t n, int G, int bits, uint32_t cap, uint32_t *scratch,
+                  uint64_t *status, uint32_t &epoch, uint32_t *offsets, uint32_t *list, uint32_t *bucket,
+                  hipStream_t st, bool counted, const std::function<bool()> &wait, uint32_t *fb_ranges,
+                  uint64_t *fb_keys, bool *whole);
 void launch_tx_masked(const TxInfo *, uint32_t, const uint64_t *, uint8_t *, hipStream_t);
 void launch_edge_check(const DEdge *, uint64_t, uint32_t, uint64_t, unsigned int *, hipStream_t);
 void launch_edge_key(const DEdge *, uint64_t, const uint32_t *, uint32_t *, uint32_t *, hipStream_t);
@@ -306,6 +317,7 @@ struct Knobs {
     uint64_t later_cap;   // RC_LATER_CAP (24 M, at least 1): searches the later-seed rounds hold states for
     bool rbh_two_pass;    // RC_RBH_TWO_PASS (unset; any value sets it): always the full second RBH pass
     int resume;           // RC_RESUME (unset = -1: by the last run's overflows): 1 = always save 32-lane states, 0 = never
+    uint32_t index_cap;   // RC_INDEX_CAP (unset = 0: the local sort's capacity; else at least 2): main-index ranges of more keys count as oversized (tests: the fallbacks)
 };
 
 static Knobs read_knobs()
@@ -324,6 +336,7 @@ static Knobs read_knobs()
     k.later_cap = env("RC_LATER_CAP") ? (uint64_t)std::max(atoll(env("RC_LATER_CAP")), 1ll) : (24ull << 20);
     k.rbh_two_pass = env("RC_RBH_TWO_PASS") != nullptr;
     k.resume = num("RC_RESUME", -1);
+    k.index_cap = env("RC_INDEX_CAP") ? (uint32_t)std::max(2, num("RC_INDEX_CAP", 2)) : 0u;
     return k;
 }
 
@@ -438,6 +451,8 @@ struct rc_engine {
     DBuf<uint32_t> d_sort_scratch;
     DBuf<uint64_t> d_sort_status;
     uint32_t sort_epoch = 0;
+    // the main index's range offsets (2^G + 1) and its list of oversized ranges
+    DBuf<uint32_t> d_range_off, d_range_list;
     DBuf<uint32_t> d_bucket;
     DBuf<PosTx> d_pos_tx;
     DBuf<uint64_t> d_sample_pos, d_txstart, d_kpos_rel, d_dmask, d_dust_imp;
@@ -1202,35 +1217,62 @@ static int load_tile(rc_engine *e, int ti)
 // 2^extra), at most 2^INDEX_BITS_MAX (28 measured best at C3 -- a 1 GiB table
 // instead of 4 GiB, same seed-kernel time). counted: the fill left the
 // sort's segment histograms in d_sort_scratch.
+// G < 0 (the near-mask index; a main index of more entries than two global
+// passes cut into LDS-sized ranges): 8-bit passes over the bits [bb, 64), then
+// the bucket fill's pass over the sorted entries. G >= 0 (the main index, bb
+// = 32): sort.hip's os_index_sort -- global passes on the top G k-mer bits, the
+// rest and the bucket table per range in LDS.
 constexpr int INDEX_BITS_MAX = 28;
-static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, uint64_t npos, unsigned bb, int extra,
-                      DBuf<uint32_t> &bucket, int &bits_out, bool counted = false)
+static int index_bits(uint64_t npos, int extra)
 {
+    int bits = 16;
+    while (bits < INDEX_BITS_MAX && (1ull << bits) < (npos << extra)) bits++;
+    return bits;
+}
+static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, uint64_t npos, unsigned bb, int extra,
+                      DBuf<uint32_t> &bucket, int &bits_out, bool counted = false, int G = -1)
+{
+    const int bits = index_bits(npos, extra);
+    bits_out = bits;
+    CHK(bucket.ensure((1ull << bits) + 1));
+    bool table_done = false;
     if (npos) {
-        // sort.hip: 8-bit LSD passes ping-ponging between the two buffers;
         // the result must end in ent2
         if (npos > 0xFFFFFFFFull) return fail(RC_E_LIMIT, "more than 2^32 index entries");
-        CHK(e->d_sort_scratch.ensure(os_scratch_words(npos)));
-        const uint64_t words = os_status_words(npos);
+        CHK(e->d_sort_scratch.ensure(G >= 0 ? os_index_scratch_words(npos) : os_scratch_words(npos)));
+        const uint64_t words = G >= 0 ? os_index_status_words(npos) : os_status_words(npos);
         if (e->d_sort_status.cap < words) {
             CHK(e->d_sort_status.ensure(words));
             HIPCHK(hipMemsetAsync(e->d_sort_status.p, 0, words * sizeof(uint64_t), e->st));
         }
-        // (no callback after the table kernels, no key generator: keys come from the entry array)
-        const bool in_alt = os_sort_keys(ent.p, ent2.p, npos, (int)bb, e->d_sort_scratch.p, e->d_sort_status.p,
-                                         e->sort_epoch, e->st, nullptr, counted, nullptr, nullptr, nullptr, 0u,
-                                         nullptr);
+        bool in_alt;
+        if (G >= 0) {
+            CHK(e->d_range_off.ensure(os_index_offset_words(G)));
+            CHK(e->d_range_list.ensure(os_index_list_words()));
+            uint32_t fb_ranges = 0;
+            uint64_t fb_keys = 0;
+            bool whole = false;
+            const int where = os_index_sort(ent.p, ent2.p, npos, G, bits, e->knobs.index_cap, e->d_sort_scratch.p,
+                                            e->d_sort_status.p, e->sort_epoch, e->d_range_off.p, e->d_range_list.p,
+                                            bucket.p, e->st, counted, [e] { return wait_st(e) == RC_OK; }, &fb_ranges,
+                                            &fb_keys, &whole);
+            if (where < 0) return fail(RC_E_HIP, "the index sort's read of its oversized ranges failed");
+            in_alt = where == 1;
+            table_done = !whole;
+            e->tm.index_fb_ranges += (double)fb_ranges;
+            e->tm.index_fb_keys += (double)fb_keys;
+        } else {
+            // (no callback after the table kernels, no key generator: keys come from the entry array)
+            in_alt = os_sort_keys(ent.p, ent2.p, npos, (int)bb, e->d_sort_scratch.p, e->d_sort_status.p,
+                                  e->sort_epoch, e->st, nullptr, counted, nullptr, nullptr, nullptr, 0u, nullptr);
+        }
         HIPCHK(hipGetLastError());
         if (!in_alt) {
             std::swap(ent.p, ent2.p);
             std::swap(ent.cap, ent2.cap);
         }
     }
-    int bits = 16;
-    while (bits < INDEX_BITS_MAX && (1ull << bits) < (npos << extra)) bits++;
-    bits_out = bits;
-    CHK(bucket.ensure((1ull << bits) + 1));
-    launch_bucket_fill(ent2.p, npos, bits, bucket.p, e->st);
+    if (!table_done) launch_bucket_fill(ent2.p, npos, bits, bucket.p, e->st);
     return RC_OK;
 }
 
@@ -1259,10 +1301,16 @@ static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64
     }
     CHK(ent.ensure(std::max<uint64_t>(npos, 1)));
     CHK(ent2.ensure(std::max<uint64_t>(npos, 1)));
-    // without ambiguity codes the fill also counts the sort's segment
-    // histograms (sort.hip), so the sort does not read the keys to count them
+    // without ambiguity codes the fill also counts the segment histograms of
+    // the sort's global passes (sort.hip), so the sort does not read the keys
+    // to count them
     const bool counted = !amb && npos > 0 && npos <= 0xFFFFFFFFull;
-    if (counted) {
+    // (G < 0: too many entries for ranges that fit the local sort; the 8-bit passes)
+    const int G = os_index_gbits(npos, index_bits(npos, 0), e->knobs.index_cap);
+    if (counted && G >= 0) {
+        CHK(e->d_sort_scratch.ensure(os_index_scratch_words(npos)));
+        os_index_fill_hist(txl, n_tx, e->d_F.p + FRONT_PAD, offs, ent.p, npos, G, e->d_sort_scratch.p, e->st);
+    } else if (counted) {
         CHK(e->d_sort_scratch.ensure(os_scratch_words(npos)));
         os_fill_hist(txl, n_tx, e->d_F.p + FRONT_PAD, offs, ent.p, npos, e->d_sort_scratch.p, e->st);
     } else if (n_tx) {
@@ -1271,7 +1319,7 @@ static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64
     }
     // sort on the k-mer (bits 32..63); the fill order is position order and the
     // radix sort is stable, so positions stay ascending per k-mer
-    CHK(sort_index(e, ent, ent2, npos, 32u, 0, bucket, bits_out, counted));
+    CHK(sort_index(e, ent, ent2, npos, 32u, 0, bucket, bits_out, counted, G));
     n_out = npos;
     return RC_OK;
 }
@@ -3261,6 +3309,7 @@ int rc_trim(rc_engine *e)
     e->d_rseeds.release(); e->d_rseed_gene.release(); e->d_rs_key.release(); e->d_rs_idx.release();
     e->d_rs_range.release(); e->d_rctr.release(); e->d_rtmask.release(); e->d_trange.release(); e->d_rtrange.release();
     e->d_ent.release(); e->d_ent2.release(); e->d_sort_scratch.release();
+    e->d_range_off.release(); e->d_range_list.release();
     e->d_sort_status.release(); e->d_bucket.release(); e->d_pos_tx.release(); e->d_sample_pos.release();
     e->d_txstart.release(); e->d_dmask.release(); e->d_dust_scratch.release(); e->d_dust_events.release();
     e->d_prof.release(); e->d_tmp.release(); e->d_seeds.release(); e->d_cands.release();

@@ -3,6 +3,10 @@
 // the product. Cases: C3-size conserved k-mers (bits 32..63), a skewed set
 // (a third of the keys share one k-mer, as poly-A windows do), small and
 // ragged sizes, and the near-mask index's full 64-bit sort.
+// OS_INDEX=1: instead, the main index's pieces at size n -- two 8-bit passes
+// against two 9-bit passes over the top 16 / 18 bits, then os_index_sort
+// (G from os_index_gbits, 28 bucket bits at full size) checked whole against
+// rocPRIM's sort and a searched bucket table, on the flat and the skewed set.
 // Usage: onesweep_micro [n]   (default 1.6e9)
 #include <cstdio>
 #include "../../rna_clique_amd/csrc/sort.hip"
@@ -60,10 +64,10 @@ int main(int argc, char **argv)
     CK(hipMalloc(&b, N * 8));
     CK(hipMalloc(&ref, N * 8));
     uint32_t *scratch;
-    CK(hipMalloc(&scratch, os_scratch_words(N) * 4));
+    CK(hipMalloc(&scratch, os_index_scratch_words(N) * 4));
     uint64_t *status;
-    CK(hipMalloc(&status, os_status_words(N) * 8));
-    CK(hipMemset(status, 0, os_status_words(N) * 8));
+    CK(hipMalloc(&status, os_index_status_words(N) * 8));
+    CK(hipMemset(status, 0, os_index_status_words(N) * 8));
     unsigned long long *bad;
     CK(hipMalloc(&bad, 8));
     void *tmp = nullptr;
@@ -91,6 +95,79 @@ int main(int argc, char **argv)
         CK(hipEventSynchronize(e1));
         CK(hipEventElapsedTime(&ms, e0, e1));
         printf("copy of %llu keys: %.3f ms = %.0f GB/s (read + write)\n", (unsigned long long)N, ms, 16.0 * N / ms / 1e6);
+    }
+    if (getenv("OS_INDEX")) {
+        int bits = 16;
+        while (bits < 28 && (1ull << bits) < N) bits++;
+        const int G = os_index_gbits(N, bits, 0);
+        uint32_t *offs, *list, *bucket, *bref;
+        CK(hipMalloc(&offs, os_index_offset_words(G) * 4));
+        CK(hipMalloc(&list, os_index_list_words() * 4));
+        CK(hipMalloc(&bucket, ((1ull << bits) + 1) * 4));
+        CK(hipMalloc(&bref, ((1ull << bits) + 1) * 4));
+        auto timed = [&](const char *what, const std::function<void()> &f) {
+            float best = 1e30f;
+            for (int rep = 0; rep < 3; rep++) {
+                CK(hipMemcpyAsync(a, src, N * 8, hipMemcpyDeviceToDevice, st));
+                CK(hipEventRecord(e0, st));
+                f();
+                CK(hipEventRecord(e1, st));
+                CK(hipEventSynchronize(e1));
+                CK(hipGetLastError());
+                float ms;
+                CK(hipEventElapsedTime(&ms, e0, e1));
+                best = std::min(best, ms);
+            }
+            printf("  %-44s %8.3f ms\n", what, best);
+        };
+        for (int kind = 0; kind < 2; kind++) {
+            hipLaunchKernelGGL(gen, dim3(8192), dim3(256), 0, st, src, N, kind);
+            printf("n=%llu kind=%d G=%d bits=%d\n", (unsigned long long)N, kind, G, bits);
+            timed("count + two 8-bit passes, bits [48, 64)", [&] {
+                sort_passes<8>(a, b, N, byte_passes(48, 64), scratch, status, epoch, st, nullptr, false, nullptr);
+            });
+            timed("count + the 9-bit global passes, top G bits", [&] {
+                sort_passes<9>(a, b, N, index_passes(G), scratch, status, epoch, st, nullptr, false, nullptr);
+            });
+            timed("four 8-bit passes, bits [32, 64)", [&] {
+                os_sort_keys(a, b, N, 32, scratch, status, epoch, st, nullptr, false, nullptr, nullptr, nullptr, 0, nullptr);
+            });
+            int where = 0;
+            uint32_t fr = 0;
+            uint64_t fk = 0;
+            bool whole = false;
+            timed("os_index_sort (with the bucket table)", [&] {
+                where = os_index_sort(a, b, N, G, bits, 0, scratch, status, epoch, offs, list, bucket, st, false,
+                                      [&] { return hipStreamSynchronize(st) == hipSuccess; }, &fr, &fk, &whole);
+            });
+            printf("  fallback: %u ranges, %llu keys, whole %d\n", fr, (unsigned long long)fk, (int)whole);
+            // (the reference sorts all 64 bits below 2^20 keys, as below: positions ascend in src)
+            const unsigned rbb = N <= (1u << 20) ? 0u : 32u;
+            size_t t = 0;
+            CK(rocprim::radix_sort_keys(nullptr, t, src, ref, (size_t)N, rbb, 64u, st));
+            CK(rocprim::radix_sort_keys(tmp, t, src, ref, (size_t)N, rbb, 64u, st));
+            CK(hipMemsetAsync(bad, 0, 8, st));
+            hipLaunchKernelGGL(cmp, dim3(8192), dim3(256), 0, st, where == 1 ? b : a, ref, N, bad);
+            unsigned long long nb = 0, nbb = 0;
+            CK(hipMemcpy(&nb, bad, 8, hipMemcpyDeviceToHost));
+            if (!whole) {
+                const uint32_t nx = 1u << bits;
+                hipLaunchKernelGGL(bucket_range_kernel, dim3(nx / 256), dim3(256), 0, st, ref, 0u, (uint32_t)N, bits, 0u,
+                                   nx, bref);
+                CK(hipMemcpyAsync(bref + nx, bucket + nx, 4, hipMemcpyDeviceToDevice, st));
+                CK(hipMemsetAsync(bad, 0, 8, st));
+                hipLaunchKernelGGL(cmp, dim3(8192), dim3(256), 0, st, (const uint64_t *)bucket, (const uint64_t *)bref,
+                                   (uint64_t)nx / 2, bad);
+                CK(hipMemcpy(&nbb, bad, 8, hipMemcpyDeviceToHost));
+                uint32_t sentinel = 0;
+                CK(hipMemcpy(&sentinel, bucket + nx, 4, hipMemcpyDeviceToHost));
+                nbb += sentinel != (uint32_t)N;
+            }
+            printf("  where %d  entry mismatches %llu  bucket mismatches %llu\n", where, nb, nbb);
+            fails += where < 0 || nb != 0 || nbb != 0;
+        }
+        printf(fails ? "FAIL\n" : "OK\n");
+        return fails ? 1 : 0;
     }
     if (getenv("OS_ONLY_BIG")) cases.resize(2);
     for (const Case &c : cases) {
