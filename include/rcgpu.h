@@ -157,6 +157,8 @@ typedef struct rc_timing {
     double index_fb_ranges;   /* main-index ranges too large for the range-local sort, sorted by the 8-bit
                                  passes instead (every range of an index whose list of them overflowed) */
     double index_fb_keys;     /* ... and the index entries in them */
+    double resample_ms;       /* device time of the last rc_resample's product kernel (zeroing its outputs
+                                 included; the weights' upload and the distances are outside it) */
 } rc_timing;
 
 void rc_default_opts(rc_opts *opts);
@@ -282,6 +284,41 @@ int rc_distance(rc_engine *eng, const int32_t *order, double *out);
  * samples a SampleSimilarity built from tables knows, filtered_distance.py:
  * 162-169 / similarity_computer.py:216-226: samples = the tables' keys). */
 int rc_distance_subset(rc_engine *eng, const int32_t *order, int32_t n, double *out);
+
+/* ---- per-component tables and resampling (after rc_run / rc_finish /
+ * rc_import_edges) ---------------------------------------------------------
+ * The ideal components are numbered 0..C-1 in ascending order of their lowest
+ * global gene index (genes are numbered sample-major, per sample in ascending
+ * gene id: the order of (sample id, gene id)); not the reference's order
+ * (get_ideal_components follows graph insertion order). A table row (an edge
+ * record) counts where rc_pair_sums counts it -- both endpoints in ideal
+ * components -- and belongs to the component of its higher sample's gene (the
+ * table's qsample/qgene, export_orthologs.py:679-684); summed over the
+ * components the sums are rc_pair_sums exactly. The tables are built on the
+ * device by the first of these calls after a graph phase and kept there
+ * (24 bytes per component and pair) until the next one; rc_trim keeps them.
+ *
+ * rc_ideal_components: members, n_comp x sample_count entries (sample, gene
+ * id), ascending sample within a component. NULL buffers query the sizes. */
+int rc_ideal_components(rc_engine *eng, int32_t *sample, int32_t *gene, uint64_t cap_nodes, uint64_t *n_comp,
+                        int32_t *sample_count);
+/* num/den: n_comp x n_pairs row-major, pairs in rc_pair_order numbering.
+ * NULL buffers query the sizes. */
+int rc_component_sums(rc_engine *eng, int64_t *num, int64_t *den, uint64_t cap_cells, uint64_t *n_comp,
+                      uint64_t *n_pairs);
+/* Replicates: num[r][p] = sum over components c of weights[r][c] * num[c][p],
+ * the same for den, and the distances (den - num) / den of each replicate.
+ * weights: n_rep x n_comp row-major (n_comp must be the engine's count). out:
+ * n_rep x n x n distances for order[n] (may be NULL); num/den: n_rep x n_pairs
+ * (may be NULL, both or neither). RC_E_NO_IDEAL after filling the outputs
+ * when some entry of out has den == 0 (it is NaN). RC_E_LIMIT when a
+ * component sum is 2^32 or more (stacked sums-only records of an imported
+ * graph), or when max(weights) x the largest rc_pair_sums denominator reaches
+ * 2^63 (the replicate sums could overflow). A bootstrap draws each row from
+ * multinomial(n_comp, 1/n_comp); a delete-one jackknife or a block deletion
+ * is a 0/1 matrix; all ones give rc_pair_sums and rc_distance. */
+int rc_resample(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                int32_t n, double *out, int64_t *num, int64_t *den);
 int rc_timings(rc_engine *eng, rc_timing *t);
 /* The DUST mask of sample `s` after rc_run / rc_align: one byte per base of
  * its concatenated transcripts (1 = masked query base, spec 1b of the oracle);

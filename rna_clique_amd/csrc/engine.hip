@@ -99,6 +99,18 @@ void launch_pair_sums(const DEdge *, uint64_t, const uint32_t *, const uint8_t *
                       unsigned long long *, unsigned long long *, unsigned long long *, hipStream_t);
 void launch_distance(const unsigned long long *, const unsigned long long *, const int32_t *, const int32_t *,
                      int, int, double *, unsigned int *, hipStream_t);
+// components.hip
+void launch_comp_keys(const uint32_t *, const uint32_t *, const uint8_t *, const uint32_t *, uint32_t, uint64_t *,
+                      unsigned long long *, hipStream_t);
+void launch_comp_members(const uint64_t *, uint64_t, uint32_t, uint32_t *, unsigned long long *, hipStream_t);
+void launch_comp_sums(const DEdge *, uint64_t, const uint32_t *, const uint8_t *, const uint32_t *, uint64_t,
+                      unsigned long long *, unsigned long long *, hipStream_t);
+void launch_comp_pack(const unsigned long long *, const unsigned long long *, uint64_t, uint2 *, unsigned long long *,
+                      hipStream_t);
+bool launch_resample(const uint2 *, const uint16_t *, uint64_t, uint64_t, uint32_t, unsigned long long *,
+                     unsigned long long *, hipStream_t);
+void launch_resample_distance(const unsigned long long *, const unsigned long long *, const int32_t *, const int32_t *,
+                              int, int, uint64_t, uint64_t, double *, unsigned int *, hipStream_t);
 }  // namespace rcg
 
 using namespace rcg;
@@ -513,6 +525,16 @@ struct rc_engine {
     DBuf<unsigned long long> d_stats, d_num, d_den, d_num_all, d_den_all;
     DBuf<int32_t> d_order;
     DBuf<double> d_dist;
+    // per-component tables (components.hip), built by the first call that
+    // needs them after a graph phase and dropped by the next one: rank of each
+    // gene's ideal[] prefix, members [C][S], sums [C][P] and their 32-bit copy
+    bool comp_valid = false;
+    uint64_t comp_n = 0, comp_max_cell = 0;
+    uint32_t comp_S = 0;
+    DBuf<uint32_t> d_crank, d_cmember;
+    DBuf<unsigned long long> d_cnum, d_cden, d_cstat, d_rnum, d_rden;
+    DBuf<uint2> d_ccell;
+    DBuf<uint16_t> d_rweight;
 
     // host results
     std::vector<unsigned long long> h_num, h_den, h_num_all, h_den_all, h_stats;
@@ -2561,6 +2583,7 @@ static int do_graph(rc_engine *e)
 {
     if (!e->rbh_done) return fail(RC_E_STATE, "graph phase before rc_finish");
     CHK(set_device(e));
+    e->comp_valid = false;   // the per-component tables follow the graph
     const int N = (int)e->samples.size();
     const uint32_t n_genes = (uint32_t)e->gene_sample.size();
     const size_t np = e->pair_a.size();
@@ -2999,6 +3022,202 @@ int rc_distance(rc_engine *e, const int32_t *order, double *out)
     if (!e) return fail(RC_E_ARG, "null argument");
     return rc_distance_subset(e, order, (int32_t)e->samples.size(), out);
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// per-component tables and resampling (kernels: components.hip)
+// ------------------------------------------------------------------------
+
+enum { CS_MEMBERS = 0, CS_MAXCELL = 1, CS_BAD = 2, CS_N = 4 };   // slots of d_cstat
+
+// The tables of the finished graph phase, built once per graph: ranks (the
+// exclusive scan of d_ideal), members, sums, their packed copy and the largest
+// cell. They stay on the device until the next do_graph.
+static int build_components(rc_engine *e)
+{
+    if (!e->finished) return fail(RC_E_STATE, "no results yet");
+    if (e->comp_valid) return RC_OK;
+    CHK(set_device(e));
+    const uint32_t ng = (uint32_t)e->gene_sample.size();
+    const uint64_t P = e->pair_a.size();
+    const uint64_t S = e->h_stats[4];
+    uint64_t C = 0;
+    CHK(e->d_crank.ensure(ng));
+    CHK(e->d_cstat.ensure(CS_N));
+    HIPCHK(hipMemsetAsync(e->d_cstat.p, 0, CS_N * sizeof(unsigned long long), e->st));
+    if (ng) {
+        size_t tmp = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->d_ideal.p, e->d_crank.p, 0u, (size_t)ng,
+                                       rocprim::plus<uint32_t>(), e->st));
+        CHK(e->d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->d_tmp.p, tmp, e->d_ideal.p, e->d_crank.p, 0u, (size_t)ng,
+                                       rocprim::plus<uint32_t>(), e->st));
+        uint32_t last_rank = 0;
+        uint8_t last_ideal = 0;
+        HIPCHK(hipMemcpyAsync(&last_rank, e->d_crank.p + ng - 1, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&last_ideal, e->d_ideal.p + ng - 1, 1, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipStreamSynchronize(e->st));
+        C = (uint64_t)last_rank + last_ideal;
+    }
+    if (C != e->h_stats[1]) return fail(RC_E_STATE, "the ideal[] scan disagrees with the ideal component count");
+    if (C && !S) return fail(RC_E_STATE, "ideal components without a sample count");
+    // members: sort (component id, gene) keys, the members come first
+    const uint64_t nm = C * S;
+    CHK(e->d_cmember.ensure(nm));
+    if (nm) {
+        DBuf<uint64_t> k0, k1;
+        CHK(k0.ensure(ng));
+        CHK(k1.ensure(ng));
+        launch_comp_keys(e->d_parent.p, e->d_present.p, e->d_ideal.p, e->d_crank.p, ng, k0.p,
+                         e->d_cstat.p + CS_MEMBERS, e->st);
+        HIPCHK(hipGetLastError());
+        size_t tmp = 0;
+        HIPCHK(rocprim::radix_sort_keys(nullptr, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
+        CHK(e->d_tmp.ensure(tmp));
+        HIPCHK(rocprim::radix_sort_keys(e->d_tmp.p, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
+        unsigned long long members = 0;
+        HIPCHK(hipMemcpyAsync(&members, e->d_cstat.p + CS_MEMBERS, 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipStreamSynchronize(e->st));
+        if (members != nm) return fail(RC_E_STATE, "ideal components do not hold sample_count members each");
+        launch_comp_members(k1.p, nm, (uint32_t)S, e->d_cmember.p, e->d_cstat.p + CS_BAD, e->st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->st));   // k0, k1 go out of scope
+    }
+    // sums, packed cells, largest cell
+    const uint64_t cells = C * P;
+    CHK(e->d_cnum.ensure(cells));
+    CHK(e->d_cden.ensure(cells));
+    CHK(e->d_ccell.ensure(cells));
+    if (cells) {
+        HIPCHK(hipMemsetAsync(e->d_cnum.p, 0, cells * 8, e->st));
+        HIPCHK(hipMemsetAsync(e->d_cden.p, 0, cells * 8, e->st));
+        launch_comp_sums(e->d_edges.p, e->n_edges, e->d_parent.p, e->d_ideal.p, e->d_crank.p, P, e->d_cnum.p,
+                         e->d_cden.p, e->st);
+        launch_comp_pack(e->d_cnum.p, e->d_cden.p, cells, e->d_ccell.p, e->d_cstat.p + CS_MAXCELL, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long st[CS_N] = {};
+    HIPCHK(hipMemcpyAsync(st, e->d_cstat.p, sizeof st, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    if (st[CS_BAD]) return fail(RC_E_STATE, "ideal components do not hold sample_count members each");
+    e->comp_n = C;
+    e->comp_S = (uint32_t)S;
+    e->comp_max_cell = st[CS_MAXCELL];
+    e->comp_valid = true;
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_ideal_components(rc_engine *e, int32_t *sample, int32_t *gene, uint64_t cap_nodes, uint64_t *n_comp,
+                        int32_t *sample_count)
+{
+    if (!e || !n_comp || !sample_count) return fail(RC_E_ARG, "null argument");
+    CHK(build_components(e));
+    *n_comp = e->comp_n;
+    *sample_count = (int32_t)e->comp_S;
+    if (!sample && !gene) return RC_OK;
+    if (!sample || !gene) return fail(RC_E_ARG, "null argument");
+    const uint64_t nm = e->comp_n * e->comp_S;
+    if (cap_nodes < nm) return fail(RC_E_CAPACITY, "buffer too small");
+    if (!nm) return RC_OK;
+    std::vector<uint32_t> m(nm);
+    HIPCHK(hipMemcpy(m.data(), e->d_cmember.p, nm * 4, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < nm; i++) {
+        sample[i] = e->gene_sample[m[i]];
+        gene[i] = e->gene_id[m[i]];
+    }
+    return RC_OK;
+}
+
+int rc_component_sums(rc_engine *e, int64_t *num, int64_t *den, uint64_t cap_cells, uint64_t *n_comp,
+                      uint64_t *n_pairs)
+{
+    if (!e || !n_comp || !n_pairs) return fail(RC_E_ARG, "null argument");
+    CHK(build_components(e));
+    *n_comp = e->comp_n;
+    *n_pairs = e->pair_a.size();
+    if (!num && !den) return RC_OK;
+    if (!num || !den) return fail(RC_E_ARG, "null argument");
+    const uint64_t cells = e->comp_n * e->pair_a.size();
+    if (cap_cells < cells) return fail(RC_E_CAPACITY, "buffer too small");
+    if (!cells) return RC_OK;
+    HIPCHK(hipMemcpy(num, e->d_cnum.p, cells * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(den, e->d_cden.p, cells * 8, hipMemcpyDeviceToHost));
+    return RC_OK;
+}
+
+int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                int32_t n, double *out, int64_t *num, int64_t *den)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    CHK(build_components(e));
+    const uint64_t C = e->comp_n, P = e->pair_a.size();
+    const int N = (int)e->samples.size();
+    if (n_comp != C) return fail(RC_E_ARG, "n_comp is not the number of ideal components");
+    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
+    if (C && !weights) return fail(RC_E_ARG, "null argument");
+    if ((num == nullptr) != (den == nullptr)) return fail(RC_E_ARG, "num and den go together");
+    if (n < 0 || n > N || (out && n && !order)) return fail(RC_E_ARG, "bad sample count");
+    if (out) {
+        std::vector<int> seen(N, 0);
+        for (int i = 0; i < n; i++) {
+            if (order[i] < 0 || order[i] >= N || seen[order[i]])
+                return fail(RC_E_ARG, "order must hold distinct sample ids");
+            seen[order[i]] = 1;
+        }
+    }
+    if (e->comp_max_cell >> 32) return fail(RC_E_LIMIT, "a component sum of 2^32 or more (stacked sums-only records)");
+    const uint64_t R = (uint64_t)n_rep;
+    uint16_t maxw = 0;
+    for (uint64_t i = 0, nw = R * C; i < nw; i++) maxw = std::max(maxw, weights[i]);
+    unsigned long long maxden = 0;
+    for (unsigned long long d : e->h_den) maxden = std::max(maxden, d);
+    // max weight x largest pair denominator bounds every replicate sum
+    if (maxw && maxden >= ((1ull << 63) + maxw - 1) / maxw)
+        return fail(RC_E_LIMIT, "weights this large could overflow the 64-bit replicate sums");
+    CHK(set_device(e));
+    const uint64_t cells = R * P;
+    CHK(e->d_rweight.ensure(R * C));
+    CHK(e->d_rnum.ensure(cells));
+    CHK(e->d_rden.ensure(cells));
+    if (R * C) HIPCHK(hipMemcpyAsync(e->d_rweight.p, weights, R * C * 2, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipEventRecord(e->ev[12], e->st));
+    if (cells) {
+        HIPCHK(hipMemsetAsync(e->d_rnum.p, 0, cells * 8, e->st));
+        HIPCHK(hipMemsetAsync(e->d_rden.p, 0, cells * 8, e->st));
+        if (!launch_resample(e->d_ccell.p, e->d_rweight.p, C, P, (uint32_t)n_rep, e->d_rnum.p, e->d_rden.p, e->st))
+            return fail(RC_E_LIMIT, "n_rep x pairs beyond the resample grid");
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->ev[13], e->st));
+    unsigned int status = 0;
+    const uint64_t nd = out ? R * (uint64_t)n * (uint64_t)n : 0;
+    if (nd) {
+        CHK(e->d_order.ensure(n));
+        CHK(e->d_dist.ensure(nd));
+        HIPCHK(hipMemcpyAsync(e->d_order.p, order, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
+        HIPCHK(hipMemsetAsync(e->d_status.p, 0, sizeof(unsigned int), e->st));
+        launch_resample_distance(e->d_rnum.p, e->d_rden.p, e->d_pair_index.p, e->d_order.p, N, n, R, P, e->d_dist.p,
+                                 e->d_status.p, e->st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, e->d_dist.p, nd * 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&status, e->d_status.p, 4, hipMemcpyDeviceToHost, e->st));
+    }
+    if (num && cells) {
+        HIPCHK(hipMemcpyAsync(num, e->d_rnum.p, cells * 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(den, e->d_rden.p, cells * 8, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.resample_ms = ev_ms(e, 12, 13);
+    if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    return RC_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int rc_dust_mask(rc_engine *e, int32_t s, uint8_t *buf, uint64_t cap, uint64_t *n)
 {

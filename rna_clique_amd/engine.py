@@ -257,6 +257,80 @@ class Engine:
                                                out.ctypes.data_as(ctypes.c_void_p)))
         return [self.labels[i] for i in order], out
 
+    # ------------------------------------------- components and resampling
+    def ideal_components(self):
+        """(sample, gene) int32 arrays of shape (C, S): the members of every
+        ideal component, components in ascending order of their lowest
+        (sample id, gene id) node -- not the reference's enumeration order --
+        and ascending sample within a component."""
+        L = nat.lib()
+        c, sc = ctypes.c_uint64(), ctypes.c_int32()
+        nat.check(L.rc_ideal_components(self._h, None, None, 0, ctypes.byref(c), ctypes.byref(sc)))
+        s = np.zeros((c.value, sc.value), dtype=np.int32)
+        g = np.zeros((c.value, sc.value), dtype=np.int32)
+        if s.size:
+            nat.check(L.rc_ideal_components(self._h, s.ctypes.data_as(ctypes.c_void_p),
+                                            g.ctypes.data_as(ctypes.c_void_p), s.size, ctypes.byref(c),
+                                            ctypes.byref(sc)))
+        return s, g
+
+    def component_sums(self):
+        """(num, den) int64 arrays of shape (C, P): each ideal component's
+        share of every pair's restricted sums, pairs in pair_order()
+        numbering. A table row belongs to the component of its higher
+        sample's gene; the sum over the components is pair_sums()."""
+        L = nat.lib()
+        c, p = ctypes.c_uint64(), ctypes.c_uint64()
+        nat.check(L.rc_component_sums(self._h, None, None, 0, ctypes.byref(c), ctypes.byref(p)))
+        num = np.zeros((c.value, p.value), dtype=np.int64)
+        den = np.zeros((c.value, p.value), dtype=np.int64)
+        if num.size:
+            nat.check(L.rc_component_sums(self._h, num.ctypes.data_as(ctypes.c_void_p),
+                                          den.ctypes.data_as(ctypes.c_void_p), num.size, ctypes.byref(c),
+                                          ctypes.byref(p)))
+        return num, den
+
+    def n_components(self):
+        c, p = ctypes.c_uint64(), ctypes.c_uint64()
+        nat.check(nat.lib().rc_component_sums(self._h, None, None, 0, ctypes.byref(c), ctypes.byref(p)))
+        return c.value
+
+    def resample(self, weights, order=None, sums=False, *, allow_nan=False):
+        """Replicate distance matrices from per-component weights (R, C),
+        integers in 0..65535: replicate r's sums are sum_c weights[r, c] *
+        component_sums()[c]. Returns (labels, ndarray (R, M, M)) in `order`
+        (default: that of distance()), plus (num, den) int64 (R, P) when
+        `sums`. Raises NativeError(RC_E_NO_IDEAL) when a replicate has a pair
+        without rows, unless allow_nan (its entries are then NaN). A bootstrap over components draws
+        each row from a multinomial (similarity.bootstrap_weights); a
+        delete-one jackknife or a block deletion is a 0/1 matrix."""
+        w = np.asarray(weights)
+        if w.ndim != 2:
+            raise ValueError("weights must have shape (replicates, components)")
+        if w.dtype != np.uint16:
+            if w.dtype.kind not in "iu":
+                raise TypeError("weights must be integers")
+            if w.size and (w.min() < 0 or w.max() > 65535):
+                raise ValueError("weights must lie in 0..65535")
+        w = np.ascontiguousarray(w, dtype=np.uint16)
+        n = len(self.labels)
+        if order is None:
+            order = sorted(range(n), key=lambda i: self.labels[i])
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        m, r = len(order), w.shape[0]
+        p = n * (n - 1) // 2
+        out = np.zeros((r, m, m), dtype=np.float64)
+        num = np.zeros((r, p), dtype=np.int64) if sums else None
+        den = np.zeros((r, p), dtype=np.int64) if sums else None
+        vp = ctypes.c_void_p
+        code = nat.lib().rc_resample(
+            self._h, w.ctypes.data_as(vp), r, w.shape[1], order.ctypes.data_as(vp), m, out.ctypes.data_as(vp),
+            num.ctypes.data_as(vp) if sums else None, den.ctypes.data_as(vp) if sums else None)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        labels = [self.labels[i] for i in order]
+        return (labels, out, (num, den)) if sums else (labels, out)
+
     def dust_mask(self, s):
         """DUST mask of sample s (uint8 per base, 1 = masked query base)."""
         return self._sized(nat.lib().rc_dust_mask, np.uint8, int(s))

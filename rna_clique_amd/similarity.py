@@ -39,6 +39,19 @@ class NoIdealComponentsError(Exception):
     pass
 
 
+def bootstrap_weights(n_components, n_rep, seed=0):
+    """Bootstrap weights over ideal components: n_rep draws of n_components
+    components with replacement, as counts -- uint16 (n_rep, n_components),
+    every row summing to n_components."""
+    c = int(n_components)
+    if c < 1:
+        return np.zeros((int(n_rep), 0), dtype=np.uint16)
+    w = np.random.default_rng(seed).multinomial(c, np.full(c, 1.0 / c), size=int(n_rep))
+    if w.max() > 65535:
+        raise ValueError("a bootstrap count above 65535")
+    return w.astype(np.uint16)
+
+
 class PairDict(dict):
     """Mapping keyed by unordered sample pairs; `d[[a, b]] == d[[b, a]]`
     (the MultisetKeyDict lookups the reference uses)."""
@@ -334,6 +347,59 @@ class SampleSimilarity:
 
     def get_dissimilarity_df(self) -> pd.DataFrame:
         return self._matrix_to_df(self.get_dissimilarity_matrix())
+
+    # ------------------------------------- ideal components and resampling
+    # Components are numbered in ascending order of their lowest (sample,
+    # gene) node in the engine's sample order -- not the reference's
+    # ideal_component_{i} numbering, which follows graph insertion order.
+    def ideal_components(self) -> pd.DataFrame:
+        """One row per ideal-component node: component, sample (label), gene;
+        components in id order, ascending engine sample inside each."""
+        s, g = self.engine.ideal_components()
+        comp = np.repeat(np.arange(s.shape[0], dtype=np.int64), s.shape[1])
+        return pd.DataFrame({"component": comp, "sample": [self.labels[i] for i in s.ravel().tolist()],
+                             "gene": g.ravel().astype(np.int64)}, columns=["component", "sample", "gene"])
+
+    def component_sums(self):
+        """(num, den) int64 (C, P): every ideal component's share of each
+        pair's restricted sums (pairs in engine.pair_order() numbering); a
+        table row belongs to the component of its qsample gene. Summed over
+        the components they are pair_sums()."""
+        return self.engine.component_sums()
+
+    def contributing_components(self) -> np.ndarray:
+        """Boolean mask over the components: those with a difference
+        somewhere, sum over pairs of (den - num) > 0 (the components
+        OrthologExporter keeps, export_orthologs.py:672-691)."""
+        num, den = self.component_sums()
+        return (den - num).sum(axis=1) > 0
+
+    def resampled_dissimilarity_matrices(self, weights) -> np.ndarray:
+        """The dissimilarity matrix of every row of `weights` (R, C; integers
+        0..65535): component c counts weights[r, c] times in replicate r.
+        Shape (R, M, M), rows and columns as get_dissimilarity_matrix(). A
+        delete-one jackknife is 1 - identity, a block deletion any other 0/1
+        matrix, a bootstrap bootstrap_weights(); all ones give
+        get_dissimilarity_matrix() itself. Raises NoIdealComponentsError when
+        a replicate leaves a pair without rows."""
+        o = self._order()
+        if not o:
+            return np.zeros((len(np.asarray(weights)), 0, 0))
+        try:
+            _, mats = self.engine.resample(weights, o)
+        except nat.NativeError as e:
+            if e.code == nat.RC_E_NO_IDEAL:
+                raise NoIdealComponentsError() from e
+            raise
+        return mats
+
+    def bootstrap_dissimilarity_matrices(self, n_rep, seed=0) -> np.ndarray:
+        """n_rep bootstrap replicates over the ideal components (weights:
+        bootstrap_weights(C, n_rep, seed)), shape (n_rep, M, M)."""
+        c = self.engine.n_components()
+        if c == 0:
+            raise NoIdealComponentsError()
+        return self.resampled_dissimilarity_matrices(bootstrap_weights(c, n_rep, seed))
 
 
 def _table_sums(df: pd.DataFrame):
