@@ -46,7 +46,8 @@ extern "C" {
  *                                 1 Mbp; 2^(36 - b) - 1 for a longest length of
  *                                 b bits (4095 at 16 Mbp)
  *   bases per alignment tile      2^32 (a shard is cut into tiles below that)
- *   seeds per (query gene, subject sample) pass 2^22 */
+ *   seeds per (query gene, subject sample) pass 2^22
+ *   samples in a neighbour-joining tree 1024 (rc_nj, rc_resample_trees) */
 #define RC_E_IO (-8)         /* file could not be written */
 
 typedef struct rc_engine rc_engine;
@@ -159,6 +160,8 @@ typedef struct rc_timing {
     double index_fb_keys;     /* ... and the index entries in them */
     double resample_ms;       /* device time of the last rc_resample's product kernel (zeroing its outputs
                                  included; the weights' upload and the distances are outside it) */
+    double nj_ms;             /* device time of the last rc_nj / rc_resample_trees' tree and support kernels
+                                 (uploads and the copies back are outside it) */
 } rc_timing;
 
 void rc_default_opts(rc_opts *opts);
@@ -319,6 +322,41 @@ int rc_component_sums(rc_engine *eng, int64_t *num, int64_t *den, uint64_t cap_c
  * is a 0/1 matrix; all ones give rc_pair_sums and rc_distance. */
 int rc_resample(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
                 int32_t n, double *out, int64_t *num, int64_t *den);
+
+/* ---- neighbour-joining trees and split support ---------------------------
+ * Saitou & Nei's neighbour joining in float64 with a fixed operation order, so
+ * that a tree is reproducible bit for bit: of matrix
+ * D[n][n] only i < j is read. While more than 3 slots are active: r[i] is the
+ * sum of column i in ascending row order; the pair (i < j) of the smallest
+ * ((n' - 2) * D[i][j] - r[i]) - r[j] is joined, ties to the lowest i, then the
+ * lowest j (n' = active slots); the new node takes slot i, the last slot moves
+ * into slot j. Leaves are nodes 0..n-1 (positions of the matrix), internal
+ * nodes n, n+1, ... in creation order.
+ *   joins[t]   children of join t (the node n + t), the third is -1 except in
+ *              the last join, which joins the three remaining nodes
+ *   lengths[t] the children's branch lengths (0 beside a -1; not clamped: a
+ *              non-additive matrix may give negative ones)
+ *   splits[t]  the leaves under join t as a bitmask over matrix positions in
+ *              W = ceil(n / 64) 64-bit words (bit b of word w = position
+ *              64 w + b), complemented within n bits when it holds position 0;
+ *              n - 3 per tree, all non-trivial and distinct
+ *   valid[r]   0 for a matrix with a non-finite entry above its diagonal: its
+ *              joins are -1, its lengths NaN, its splits 0
+ * support[k] = the number of valid replicates whose tree has reference split
+ * ref_splits[k] (n_ref x W words in the same form); n_valid = the number of
+ * valid replicates. Any output may be NULL; support needs ref_splits.
+ * RC_E_ARG: n < 3, n_rep < 1, or a reference split that holds position 0 or a
+ * bit at or above n. RC_E_LIMIT: n > 1024. RC_E_NO_IDEAL after filling the
+ * outputs when some matrix is invalid.
+ * rc_nj: the trees of n_rep caller matrices (host, n_rep x n x n), on an
+ * engine in any state. rc_resample_trees: the trees of rc_resample's replicate
+ * matrices for order[n], which never leave the device. */
+int rc_nj(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, int32_t *joins, double *lengths,
+          uint64_t *splits, uint8_t *valid, const uint64_t *ref_splits, int32_t n_ref, uint32_t *support,
+          uint32_t *n_valid);
+int rc_resample_trees(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                      int32_t n, int32_t *joins, double *lengths, uint64_t *splits, uint8_t *valid,
+                      const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid);
 int rc_timings(rc_engine *eng, rc_timing *t);
 /* The DUST mask of sample `s` after rc_run / rc_align: one byte per base of
  * its concatenated transcripts (1 = masked query base, spec 1b of the oracle);

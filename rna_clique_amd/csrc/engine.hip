@@ -111,6 +111,12 @@ bool launch_resample(const uint2 *, const uint16_t *, uint64_t, uint64_t, uint32
                      unsigned long long *, hipStream_t);
 void launch_resample_distance(const unsigned long long *, const unsigned long long *, const int32_t *, const int32_t *,
                               int, int, uint64_t, uint64_t, double *, unsigned int *, hipStream_t);
+// nj.hip
+size_t nj_lds_bytes(bool, int, int);
+hipError_t launch_nj(bool, const double *, int, int, int, double *, uint64_t *, int32_t *, double *, uint64_t *,
+                     uint8_t *, hipStream_t);
+void launch_nj_support(const uint64_t *, int, const uint64_t *, const uint8_t *, int, int, int, uint32_t *, uint32_t *,
+                       hipStream_t);
 }  // namespace rcg
 
 using namespace rcg;
@@ -330,6 +336,7 @@ struct Knobs {
     bool rbh_two_pass;    // RC_RBH_TWO_PASS (unset; any value sets it): always the full second RBH pass
     int resume;           // RC_RESUME (unset = -1: by the last run's overflows): 1 = always save 32-lane states, 0 = never
     uint32_t index_cap;   // RC_INDEX_CAP (unset = 0: the local sort's capacity; else at least 2): main-index ranges of more keys count as oversized (tests: the fallbacks)
+    int nj_lds;           // RC_NJ_LDS (128; at most 128): the most samples whose neighbour-joining matrix lives in LDS; 0 = every tree through the global workspace (tests: that path)
 };
 
 static Knobs read_knobs()
@@ -349,6 +356,7 @@ static Knobs read_knobs()
     k.rbh_two_pass = env("RC_RBH_TWO_PASS") != nullptr;
     k.resume = num("RC_RESUME", -1);
     k.index_cap = env("RC_INDEX_CAP") ? (uint32_t)std::max(2, num("RC_INDEX_CAP", 2)) : 0u;
+    k.nj_lds = std::min(128, std::max(0, num("RC_NJ_LDS", 128)));
     return k;
 }
 
@@ -535,6 +543,14 @@ struct rc_engine {
     DBuf<unsigned long long> d_cnum, d_cden, d_cstat, d_rnum, d_rden;
     DBuf<uint2> d_ccell;
     DBuf<uint16_t> d_rweight;
+    // neighbour joining (nj.hip): input matrices of rc_nj, the trees, the
+    // reference splits with their support (n_ref counters, then n_valid) and
+    // the workspace of the trees too large for LDS
+    DBuf<double> d_nj_in, d_nj_len, d_nj_wsm;
+    DBuf<int32_t> d_nj_joins;
+    DBuf<uint64_t> d_nj_splits, d_nj_ref, d_nj_wsmask;
+    DBuf<uint8_t> d_nj_valid;
+    DBuf<uint32_t> d_nj_sup;
 
     // host results
     std::vector<unsigned long long> h_num, h_den, h_num_all, h_den_all, h_stats;
@@ -3148,19 +3164,24 @@ int rc_component_sums(rc_engine *e, int64_t *num, int64_t *den, uint64_t cap_cel
     return RC_OK;
 }
 
-int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
-                int32_t n, double *out, int64_t *num, int64_t *den)
+}  // extern "C"
+
+// rc_resample up to the filled device buffers: the replicate sums in d_rnum /
+// d_rden and, with `dist`, the n_rep x n x n distances in d_dist with their
+// status word in d_status (queued on the stream, not waited for). Events
+// ev[12], ev[13].
+static int resample_fill(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                         int32_t n, bool dist, bool sums_paired)
 {
-    if (!e) return fail(RC_E_ARG, "null argument");
     CHK(build_components(e));
     const uint64_t C = e->comp_n, P = e->pair_a.size();
     const int N = (int)e->samples.size();
     if (n_comp != C) return fail(RC_E_ARG, "n_comp is not the number of ideal components");
     if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
     if (C && !weights) return fail(RC_E_ARG, "null argument");
-    if ((num == nullptr) != (den == nullptr)) return fail(RC_E_ARG, "num and den go together");
-    if (n < 0 || n > N || (out && n && !order)) return fail(RC_E_ARG, "bad sample count");
-    if (out) {
+    if (!sums_paired) return fail(RC_E_ARG, "num and den go together");
+    if (n < 0 || n > N || (dist && n && !order)) return fail(RC_E_ARG, "bad sample count");
+    if (dist) {
         std::vector<int> seen(N, 0);
         for (int i = 0; i < n; i++) {
             if (order[i] < 0 || order[i] >= N || seen[order[i]])
@@ -3192,8 +3213,7 @@ int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(e->ev[13], e->st));
-    unsigned int status = 0;
-    const uint64_t nd = out ? R * (uint64_t)n * (uint64_t)n : 0;
+    const uint64_t nd = dist ? R * (uint64_t)n * (uint64_t)n : 0;
     if (nd) {
         CHK(e->d_order.ensure(n));
         CHK(e->d_dist.ensure(nd));
@@ -3202,6 +3222,21 @@ int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n
         launch_resample_distance(e->d_rnum.p, e->d_rden.p, e->d_pair_index.p, e->d_order.p, N, n, R, P, e->d_dist.p,
                                  e->d_status.p, e->st);
         HIPCHK(hipGetLastError());
+    }
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                int32_t n, double *out, int64_t *num, int64_t *den)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, out != nullptr, (num == nullptr) == (den == nullptr)));
+    const uint64_t cells = (uint64_t)n_rep * e->pair_a.size();
+    const uint64_t nd = out ? (uint64_t)n_rep * (uint64_t)n * (uint64_t)n : 0;
+    unsigned int status = 0;
+    if (nd) {
         HIPCHK(hipMemcpyAsync(out, e->d_dist.p, nd * 8, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, 4, hipMemcpyDeviceToHost, e->st));
     }
@@ -3212,6 +3247,121 @@ int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n
     HIPCHK(hipStreamSynchronize(e->st));
     e->tm.resample_ms = ev_ms(e, 12, 13);
     if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    return RC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// neighbour joining (nj.hip)
+// ------------------------------------------------------------------------
+
+static const int NJ_MAX_SAMPLES = 1024;
+static const uint64_t NJ_WS_BYTES = 1ull << 30;   // workspace of the trees too large for LDS
+
+// the argument checks of rc_nj / rc_resample_trees (no device work)
+static int nj_check(int32_t n_rep, int32_t n, const uint64_t *ref, int32_t n_ref, const uint32_t *support)
+{
+    if (n < 3) return fail(RC_E_ARG, "a tree needs at least 3 samples");
+    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
+    if (n > NJ_MAX_SAMPLES) return fail(RC_E_LIMIT, "more than 1024 samples in a neighbour-joining tree");
+    if (n_ref < 0 || (n_ref > 0 && !ref)) return fail(RC_E_ARG, "bad reference splits");
+    if (support && !ref) return fail(RC_E_ARG, "support needs ref_splits");
+    const int W = (n + 63) / 64;
+    for (int64_t k = 0; k < n_ref; k++) {
+        if (ref[k * W] & 1ull) return fail(RC_E_ARG, "a reference split holds position 0 (pass the other side)");
+        if ((n & 63) && ref[k * W + W - 1] >> (n & 63))
+            return fail(RC_E_ARG, "a reference split has bits at or above the sample count");
+    }
+    return RC_OK;
+}
+
+// Trees of the n_rep matrices at dD (device, n x n each) and the support of
+// the reference splits; the arguments have passed nj_check. Events ev[14],
+// ev[15]. *invalid: the number of matrices with a non-finite entry.
+static int nj_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t *joins, double *lengths,
+                     uint64_t *splits, uint8_t *valid, const uint64_t *ref, int32_t n_ref, uint32_t *support,
+                     uint32_t *n_valid, uint32_t *invalid)
+{
+    const int W = (n + 63) / 64;
+    const size_t R = (size_t)n_rep, nj = R * (size_t)(n - 2) * 3, ns = R * (size_t)(n - 3) * W;
+    CHK(e->d_nj_joins.ensure(nj));
+    CHK(e->d_nj_len.ensure(nj));
+    CHK(e->d_nj_splits.ensure(ns));
+    CHK(e->d_nj_valid.ensure(R));
+    CHK(e->d_nj_ref.ensure((size_t)n_ref * W));
+    CHK(e->d_nj_sup.ensure((size_t)n_ref + 1));
+    int lds_max = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
+    const bool lds = n <= e->knobs.nj_lds && nj_lds_bytes(true, n, W) <= (size_t)lds_max;
+    const size_t per = (size_t)n * n * 8 + (size_t)n * W * 8;
+    const size_t chunk = lds ? R : std::max<size_t>(1, std::min<size_t>(R, NJ_WS_BYTES / per));
+    if (!lds) {
+        CHK(e->d_nj_wsm.ensure(chunk * n * n));
+        CHK(e->d_nj_wsmask.ensure(chunk * n * W));
+    }
+    if (n_ref) HIPCHK(hipMemcpyAsync(e->d_nj_ref.p, ref, (size_t)n_ref * W * 8, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemsetAsync(e->d_nj_sup.p, 0, ((size_t)n_ref + 1) * 4, e->st));
+    HIPCHK(hipEventRecord(e->ev[14], e->st));
+    for (size_t r0 = 0; r0 < R; r0 += chunk) {
+        const size_t rc = std::min(chunk, R - r0);
+        const hipError_t err = launch_nj(lds, dD + r0 * n * n, (int)rc, n, W, e->d_nj_wsm.p, e->d_nj_wsmask.p,
+                                         e->d_nj_joins.p + r0 * (n - 2) * 3, e->d_nj_len.p + r0 * (n - 2) * 3,
+                                         e->d_nj_splits.p + r0 * (n - 3) * W, e->d_nj_valid.p + r0, e->st);
+        if (err != hipSuccess)
+            return fail(RC_E_HIP, std::string("nj_kernel (") + std::to_string(nj_lds_bytes(lds, n, W)) +
+                                      " bytes of LDS): " + hipGetErrorString(err));
+    }
+    launch_nj_support(e->d_nj_ref.p, n_ref, e->d_nj_splits.p, e->d_nj_valid.p, n_rep, n - 3, W, e->d_nj_sup.p,
+                      e->d_nj_sup.p + n_ref, e->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->ev[15], e->st));
+    uint32_t nv = 0;
+    if (joins) HIPCHK(hipMemcpyAsync(joins, e->d_nj_joins.p, nj * 4, hipMemcpyDeviceToHost, e->st));
+    if (lengths) HIPCHK(hipMemcpyAsync(lengths, e->d_nj_len.p, nj * 8, hipMemcpyDeviceToHost, e->st));
+    if (splits && ns) HIPCHK(hipMemcpyAsync(splits, e->d_nj_splits.p, ns * 8, hipMemcpyDeviceToHost, e->st));
+    if (valid) HIPCHK(hipMemcpyAsync(valid, e->d_nj_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    if (support && n_ref)
+        HIPCHK(hipMemcpyAsync(support, e->d_nj_sup.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(&nv, e->d_nj_sup.p + n_ref, 4, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.nj_ms = ev_ms(e, 14, 15);
+    if (n_valid) *n_valid = nv;
+    *invalid = (uint32_t)n_rep - nv;
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_nj(rc_engine *e, const double *D, int32_t n_rep, int32_t n, int32_t *joins, double *lengths, uint64_t *splits,
+          uint8_t *valid, const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    CHK(nj_check(n_rep, n, ref_splits, n_ref, support));
+    if (!D) return fail(RC_E_ARG, "null argument");
+    CHK(set_device(e));
+    const size_t nd = (size_t)n_rep * n * n;
+    CHK(e->d_nj_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->d_nj_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
+    uint32_t invalid = 0;
+    CHK(nj_device(e, e->d_nj_in.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
+                  &invalid));
+    if (invalid) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no tree for it");
+    return RC_OK;
+}
+
+int rc_resample_trees(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                      int32_t n, int32_t *joins, double *lengths, uint64_t *splits, uint8_t *valid,
+                      const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    CHK(nj_check(n_rep, n, ref_splits, n_ref, support));
+    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
+    uint32_t invalid = 0;
+    CHK(nj_device(e, e->d_dist.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
+                  &invalid));
+    e->tm.resample_ms = ev_ms(e, 12, 13);
+    if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;
 }
 

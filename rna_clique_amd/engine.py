@@ -331,6 +331,79 @@ class Engine:
         labels = [self.labels[i] for i in order]
         return (labels, out, (num, den)) if sums else (labels, out)
 
+    # ------------------------------------------------ neighbour-joining trees
+    @staticmethod
+    def _nj_buffers(r, m, ref_splits):
+        from .tree import split_words
+        w = split_words(m)
+        ref = None
+        if ref_splits is not None:
+            ref = np.ascontiguousarray(ref_splits, dtype=np.uint64).reshape(-1, w)
+        bufs = {"joins": np.zeros((r, max(m - 2, 0), 3), dtype=np.int32),
+                "lengths": np.zeros((r, max(m - 2, 0), 3), dtype=np.float64),
+                "splits": np.zeros((r, max(m - 3, 0), w), dtype=np.uint64), "valid": np.zeros(r, dtype=np.uint8),
+                "support": None if ref is None else np.zeros(len(ref), dtype=np.uint32)}
+        return ref, bufs
+
+    @staticmethod
+    def _nj_args(ref, bufs, n_valid):
+        vp = ctypes.c_void_p
+        ptr = lambda a: None if a is None else a.ctypes.data_as(vp)   # noqa: E731
+        return (ptr(bufs["joins"]), ptr(bufs["lengths"]), ptr(bufs["splits"]), ptr(bufs["valid"]), ptr(ref),
+                0 if ref is None else len(ref), ptr(bufs["support"]), ctypes.byref(n_valid))
+
+    def nj(self, matrices, ref_splits=None, *, allow_nan=False):
+        """Neighbour-joining trees of distance matrices (R, N, N) or (N, N),
+        of which only the part above the diagonal is read (rc_nj; the engine
+        may be in any state). Returns tree.NJResult: joins, lengths, splits
+        and valid with a leading replicate axis, and with `ref_splits`
+        (n_ref, W) uint64 the number of valid trees that have each of them.
+        Raises NativeError(RC_E_NO_IDEAL) when a matrix has a non-finite
+        entry, unless allow_nan (that tree is then flagged in `valid`)."""
+        from .tree import NJResult
+        d = np.ascontiguousarray(matrices, dtype=np.float64)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1] != d.shape[2]:
+            raise ValueError("matrices must have shape (replicates, N, N)")
+        r, m = d.shape[0], d.shape[1]
+        ref, bufs = self._nj_buffers(r, m, ref_splits)
+        nv = ctypes.c_uint32()
+        code = nat.lib().rc_nj(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, *self._nj_args(ref, bufs, nv))
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return NJResult(n_valid=nv.value, **bufs)
+
+    def resample_trees(self, weights, order=None, ref_splits=None, *, allow_nan=False):
+        """The neighbour-joining tree of every replicate of resample(weights,
+        order): the matrices stay on the device (rc_resample_trees). Returns
+        (labels, tree.NJResult); split bit b stands for labels[b]. Raises
+        NativeError(RC_E_NO_IDEAL) when a replicate has a pair without rows,
+        unless allow_nan (that tree is then flagged in `valid`)."""
+        from .tree import NJResult
+        w = np.asarray(weights)
+        if w.ndim != 2:
+            raise ValueError("weights must have shape (replicates, components)")
+        if w.dtype != np.uint16:
+            if w.dtype.kind not in "iu":
+                raise TypeError("weights must be integers")
+            if w.size and (w.min() < 0 or w.max() > 65535):
+                raise ValueError("weights must lie in 0..65535")
+        w = np.ascontiguousarray(w, dtype=np.uint16)
+        n = len(self.labels)
+        if order is None:
+            order = sorted(range(n), key=lambda i: self.labels[i])
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        m, r = len(order), w.shape[0]
+        ref, bufs = self._nj_buffers(r, m, ref_splits)
+        nv = ctypes.c_uint32()
+        vp = ctypes.c_void_p
+        code = nat.lib().rc_resample_trees(self._h, w.ctypes.data_as(vp), r, w.shape[1], order.ctypes.data_as(vp), m,
+                                           *self._nj_args(ref, bufs, nv))
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return [self.labels[i] for i in order], NJResult(n_valid=nv.value, **bufs)
+
     def dust_mask(self, s):
         """DUST mask of sample s (uint8 per base, 1 = masked query base)."""
         return self._sized(nat.lib().rc_dust_mask, np.uint8, int(s))

@@ -401,6 +401,48 @@ class SampleSimilarity:
             raise NoIdealComponentsError()
         return self.resampled_dissimilarity_matrices(bootstrap_weights(c, n_rep, seed))
 
+    # ------------------------------------------ neighbour-joining trees
+    def _resample_trees(self, weights, ref_splits=None):
+        """Engine.resample_trees in this object's sample order."""
+        o = self._order()
+        if len(o) < 3:
+            raise ValueError("a tree needs at least 3 samples")
+        try:
+            return self.engine.resample_trees(weights, o, ref_splits)[1]
+        except nat.NativeError as e:
+            if e.code == nat.RC_E_NO_IDEAL:
+                raise NoIdealComponentsError() from e
+            raise
+
+    def resampled_trees(self, weights) -> list:
+        """The neighbour-joining tree (tree.NJTree) of every row of `weights`:
+        the trees of resampled_dissimilarity_matrices(weights), built on the
+        GPU without the matrices leaving it. Leaves are self.samples."""
+        from .tree import NJTree
+        res = self._resample_trees(weights)
+        return [NJTree(self.samples, res.joins[r], res.lengths[r], res.splits[r]) for r in range(len(res.valid))]
+
+    def neighbor_joining_tree(self):
+        """The neighbour-joining tree of get_dissimilarity_matrix() (the
+        replicate of all-ones weights, which is that matrix bit for bit):
+        DistanceTreeConstructor().nj of the tutorial's make_tree.py, unrooted."""
+        c = self.engine.n_components()
+        if c == 0:
+            if len(self._order()) < 3:
+                raise ValueError("a tree needs at least 3 samples")
+            raise NoIdealComponentsError()
+        return self.resampled_trees(np.ones((1, c), dtype=np.uint16))[0]
+
+    def bootstrap_support(self, n_rep, seed=0):
+        """neighbor_joining_tree() with support[k] = the fraction of n_rep
+        bootstrap replicates over the ideal components (bootstrap_weights(C,
+        n_rep, seed)) whose tree has split k. With exactly 3 samples: the star
+        tree with empty support."""
+        from .tree import NJTree
+        tree = self.neighbor_joining_tree()
+        res = self._resample_trees(bootstrap_weights(self.engine.n_components(), n_rep, seed), tree.splits)
+        return NJTree(tree.labels, tree.joins, tree.lengths, tree.splits, res.support / float(res.n_valid))
+
 
 def _table_sums(df: pd.DataFrame):
     """(sum nident, sum length - sum gaps) of one gene matches table, as exact
