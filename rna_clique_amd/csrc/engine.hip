@@ -73,7 +73,7 @@ void launch_tile_tables(const TileSeg *, uint32_t, uint32_t, const uint64_t *, c
                         uint32_t *, TxInfo *, uint64_t *, uint32_t, uint64_t, uint64_t *, IsoRec *, uint64_t,
                         const uint64_t *, PosTx *, uint64_t, hipStream_t);
 void launch_near_fill(bool, const TxInfo *, uint32_t, const uint8_t *, const uint64_t *, const uint64_t *,
-                      const uint64_t *, uint64_t *, uint64_t, unsigned long long *, hipStream_t);
+                      const uint64_t *, uint64_t *, uint64_t, unsigned long long *, int, hipStream_t);
 void launch_seed(bool, const Db &, const Index &, const SeedParams &, hipStream_t);
 void launch_seed_big(bool, const Db &, const Index &, const SeedParams &, uint32_t, hipStream_t);
 void launch_rs_range(const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
@@ -1373,8 +1373,9 @@ static int build_index(rc_engine *e)
 // SUBJECT a holds a masked base may have seeds the forward pass does not find
 // (runs none of whose aligned words of a is usable); every 16-mer of such a
 // run has a masked base of a nearby, so the index holds only the positions of
-// masked transcripts with a masked base in [pos - 12, pos + 28)
-// (near_fill_kernel), sorted on all 64 key bits, with 4 buckets per entry.
+// masked transcripts with a masked base in [pos - (W - 16), pos + W), W = the
+// word size (near_fill_kernel), sorted on all 64 key bits, with 4 buckets per
+// entry.
 static int build_masked_index(rc_engine *e)
 {
     const uint32_t n = e->tile_ntx;
@@ -1390,7 +1391,7 @@ static int build_masked_index(rc_engine *e)
         HIPCHK(hipMemsetAsync(e->d_rctr.p, 0, sizeof(unsigned long long), e->st));
         launch_near_fill(e->has_amb, e->d_tile_tx.p, n, e->d_tile_masked.p, e->d_F.p + FRONT_PAD,
                          e->has_amb ? e->d_AF.p + FRONT_PAD : nullptr, e->d_dmask.p + 1, e->d_ment.p, e->mnear_cap,
-                         e->d_rctr.p, e->st);
+                         e->d_rctr.p, e->o.word_size, e->st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&cnt, e->d_rctr.p, sizeof cnt, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));

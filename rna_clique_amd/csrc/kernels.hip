@@ -880,12 +880,13 @@ void launch_tx_masked(const TxInfo *txl, uint32_t n, const uint64_t *dmask, uint
 }
 
 // The reverse pass's index (shared searches with DUST): the 16-mer positions
-// of masked transcripts with a DUST-masked base in [pos - 12, pos + 28). A
-// run between a and b none of whose aligned words of a is usable has a masked
-// base of a there for every 16-mer pos it holds: the 28 bases of the run
-// nearest to [pos, pos + 16) lie in that range and hold a whole word of a's
-// grid (13 consecutive starts hold one), and that word is masked. So the hits
-// of such runs are all here. One wave per
+// of masked transcripts with a DUST-masked base in [pos - (W - 16), pos + W),
+// W = the word size ([pos - 12, pos + 28) at the default 28; 16 to 112 bits).
+// A run between a and b none of whose aligned words of a is usable has a
+// masked base of a there for every 16-mer pos it holds: the W bases of the
+// run nearest to [pos, pos + 16) lie in that range and hold a whole word of
+// a's grid (W - 15 consecutive starts hold one), and that word is masked. So
+// the hits of such runs are all here. One wave per
 // transcript, one atomic per 64 positions: the order is arbitrary and the
 // sort orders all 64 key bits. Entries past `cap` are counted, not written.
 template <bool AMB>
@@ -894,16 +895,27 @@ __global__ __launch_bounds__(256) void near_fill_kernel(const TxInfo *__restrict
                                                         const uint64_t *__restrict__ F,
                                                         const uint64_t *__restrict__ AF,
                                                         const uint64_t *__restrict__ dmask, uint64_t *__restrict__ ent,
-                                                        uint64_t cap, unsigned long long *count)
+                                                        uint64_t cap, unsigned long long *count, int word)
 {
     const int lane = threadIdx.x & 63;
+    // the range's bits before pos and in all: 0..48 and 16..112 (word_size is
+    // 16..64), read as one or two 64-bit windows. The mask has a guard word in
+    // front and three past the tile's last base: pos - back >= -48 and the
+    // second window's start pos - back + 64 <= total + 48 stay inside
+    const int back = word - W16, span = 2 * word - W16;
+    const uint64_t m0 = span >= 64 ? ~0ull : (1ull << span) - 1ull;
+    const uint64_t m1 = span > 64 ? (1ull << (span - 64)) - 1ull : 0ull;
     const uint32_t nwave = gridDim.x * 4u, t0 = blockIdx.x * 4u + (threadIdx.x >> 6);
     // the positions of this wave's transcripts: counted, one atomic for all
     // of them, then written (one counter for every wave: an atomic per 64
     // positions serialised on it)
     auto near = [&](const TxInfo &ti, int64_t o, uint64_t &p) -> bool {
         p = ti.start + (uint64_t)o;
-        bool ok = o <= (int64_t)ti.len - W16 && (win_bits(dmask, (int64_t)p - 12) & ((1ull << 40) - 1ull)) != 0;
+        bool ok = o <= (int64_t)ti.len - W16;
+        if (ok) {
+            ok = (win_bits(dmask, (int64_t)p - back) & m0) != 0;
+            if (!ok && m1) ok = (win_bits(dmask, (int64_t)p - back + 64) & m1) != 0;
+        }
         if (AMB && ok) ok = (win(AF, p) & 0xFFFFFFFFull) == 0;
         return ok;
     };
@@ -932,14 +944,16 @@ __global__ __launch_bounds__(256) void near_fill_kernel(const TxInfo *__restrict
 
 void launch_near_fill(bool amb, const TxInfo *tx, uint32_t n_tx, const uint8_t *masked, const uint64_t *F,
                       const uint64_t *AF, const uint64_t *dmask, uint64_t *ent, uint64_t cap,
-                      unsigned long long *count, hipStream_t st)
+                      unsigned long long *count, int word, hipStream_t st)
 {
     if (!n_tx) return;
     const dim3 g(std::min<uint32_t>((n_tx + 3) / 4, FILL_BLOCKS));
     if (amb)
-        hipLaunchKernelGGL(near_fill_kernel<true>, g, dim3(256), 0, st, tx, n_tx, masked, F, AF, dmask, ent, cap, count);
+        hipLaunchKernelGGL(near_fill_kernel<true>, g, dim3(256), 0, st, tx, n_tx, masked, F, AF, dmask, ent, cap, count,
+                           word);
     else
-        hipLaunchKernelGGL(near_fill_kernel<false>, g, dim3(256), 0, st, tx, n_tx, masked, F, AF, dmask, ent, cap, count);
+        hipLaunchKernelGGL(near_fill_kernel<false>, g, dim3(256), 0, st, tx, n_tx, masked, F, AF, dmask, ent, cap, count,
+                           word);
 }
 
 // After pass 2 and the scans: each item's rows and edges from its slots to
