@@ -10,7 +10,7 @@
 // epoch, kept across calls the way the engine's sort_index keeps them: the
 // status table is zeroed only when it grows, the epoch starts at 0 and is
 // advanced by os_sort_keys alone.
-#include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -19,19 +19,6 @@
 #include <vector>
 
 namespace rcg {
-void launch_pack(const uint8_t *, uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_kmer_count(const TxInfo *, uint32_t, const uint64_t *, uint64_t *, hipStream_t);
-void launch_kmer_fill(bool, const TxInfo *, uint32_t, const uint64_t *, const uint64_t *, const uint64_t *,
-                      uint64_t *, hipStream_t);
-void launch_bucket_fill(const uint64_t *, uint64_t, int, uint32_t *, hipStream_t);
-uint64_t os_status_words(uint64_t n);
-uint64_t os_scratch_words(uint64_t n);
-bool os_sort_keys(uint64_t *keys, uint64_t *alt, uint64_t n, int bb, uint32_t *scratch, uint64_t *status,
-                  uint32_t &epoch, hipStream_t st, const std::function<void()> &after_prep, bool counted,
-                  const TxInfo *gen_tx, const uint64_t *gen_koff, const uint64_t *gen_F, uint32_t gen_ntx,
-                  uint32_t *gen_tile);
-void os_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
-                  uint64_t n, uint32_t *scratch, hipStream_t st);
 int os_tile_keys();
 int os_segments();
 int bucket_fill_per_thread();
@@ -41,7 +28,7 @@ using rcg::TxInfo;
 
 namespace {
 
-constexpr size_t FRONT_PAD = 2;   // engine.hip: zero words in front of every packed array
+constexpr size_t FRONT_PAD = 2;   // engine.h: zero words in front of every packed array
 constexpr size_t BACK_PAD = 4;    // and behind
 constexpr int IP_E_ARG = -1, IP_E_HIP = -2, IP_E_CAP = -3;
 

@@ -54,7 +54,7 @@ def _product():
 
 def _deps():
     csrc = _product().CSRC
-    return [SRC] + WRAPPERS + [os.path.join(csrc, s) for s in PRODUCT_SOURCES + ["device.h"]]
+    return [SRC] + WRAPPERS + [os.path.join(csrc, s) for s in PRODUCT_SOURCES + ["device.h", "launch.h"]]
 
 
 def _stale():

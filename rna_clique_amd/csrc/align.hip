@@ -20,6 +20,7 @@
 //
 // Semantics: oracle/align_oracle.c ("RC-megablast v1"), bit for bit.
 #include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <climits>

@@ -16,6 +16,7 @@
 // between two ideal components this rule decides. Node-only records add
 // nothing. Summed over the components the table is rc_pair_sums exactly.
 #include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 

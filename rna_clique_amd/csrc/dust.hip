@@ -30,6 +30,7 @@
 //     Deferring this rare pass keeps the scan free of the long divergent
 //     loop one lane in three wave steps would otherwise impose on the wave.
 #include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 

@@ -1,206 +1,30 @@
 // Host side of the MI355X RNA-clique engine: the C ABI of include/rcgpu.h.
 //
-// Owns the device buffers, drives the kernels of kernels.hip on one HIP
-// stream, and converts results back to reference semantics (1-based BLAST
-// coordinates, pandas index labels, sorted-label matrix order).
-#include "../../include/rcgpu.h"
-#include "device.h"
-#include "graph_pickle.h"
-
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <numeric>
-#include <string>
-#include <thread>
-#include <vector>
-
-// od2_tables.cpp: one pair's gene matches table file
-int od2_write_table(const rc_row *rows, uint64_t n, const std::string &ssample, const std::string &qsample,
-                    const std::string &path);
-// graph_pickle.cpp: a table of the pickle whose gene arrays the caller fills
-extern "C" int graph_pickle_table(rc_gpickle *g, int32_t ssample, int32_t qsample, uint64_t n, int64_t **sgene,
-                                  int64_t **qgene);
-
-namespace rcg {
-void launch_pack(const uint8_t *, uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_kmer_count(const TxInfo *, uint32_t, const uint64_t *, uint64_t *, hipStream_t);
-void launch_kmer_fill(bool, const TxInfo *, uint32_t, const uint64_t *, const uint64_t *, const uint64_t *,
-                      uint64_t *, hipStream_t);
-void launch_bucket_fill(const uint64_t *, uint64_t, int, uint32_t *, hipStream_t);
-uint64_t os_status_words(uint64_t n);
-uint64_t os_scratch_words(uint64_t n);
-bool os_sort_keys(uint64_t *keys, uint64_t *alt, uint64_t n, int bb, uint32_t *scratch, uint64_t *status,
-                  uint32_t &epoch, hipStream_t st, const std::function<void()> &after_prep, bool counted,
-                  const TxInfo *gen_tx, const uint64_t *gen_koff, const uint64_t *gen_F, uint32_t gen_ntx,
-                  uint32_t *gen_tile);
-void os_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
-                  uint64_t n, uint32_t *scratch, hipStream_t st);
-int os_index_gbits(uint64_t n, int bits, uint32_t cap);
-uint64_t os_index_status_words(uint64_t n);
-uint64_t os_index_scratch_words(uint64_t n);
-uint64_t os_index_offset_words(int G);
-uint64_t os_index_list_words();
-void os_index_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
-                        uint64_t n, int G, uint32_t *scratch, hipStream_t st);
-int os_index_sort(uint64_t *keys, uint64_t *alt, uint64_t n, int G, int bits, uint32_t cap, uint32_t *scratch,
-                  uint64_t *status, uint32_t &epoch, uint32_t *offsets, uint32_t *list, uint32_t *bucket,
-                  hipStream_t st, bool counted, const std::function<bool()> &wait, uint32_t *fb_ranges,
-                  uint64_t *fb_keys, bool *whole);
-void launch_tx_masked(const TxInfo *, uint32_t, const uint64_t *, uint8_t *, hipStream_t);
-void launch_edge_check(const DEdge *, uint64_t, uint32_t, uint64_t, unsigned int *, hipStream_t);
-void launch_edge_key(const DEdge *, uint64_t, const uint32_t *, uint32_t *, uint32_t *, hipStream_t);
-void launch_edge_gather(const DEdge *, const uint32_t *, uint64_t, DEdge *, hipStream_t);
-void launch_edge_uv(const DEdge *, const uint32_t *, const uint32_t *, uint64_t, uint32_t *, uint32_t *, uint64_t *,
-                    hipStream_t);
-void launch_tile_tables(const TileSeg *, uint32_t, uint32_t, const uint64_t *, const uint64_t *, TxInfo *, TxInfo *,
-                        uint32_t *, TxInfo *, uint64_t *, uint32_t, uint64_t, uint64_t *, IsoRec *, uint64_t,
-                        const uint64_t *, PosTx *, uint64_t, hipStream_t);
-void launch_near_fill(bool, const TxInfo *, uint32_t, const uint8_t *, const uint64_t *, const uint64_t *,
-                      const uint64_t *, uint64_t *, uint64_t, unsigned long long *, int, hipStream_t);
-void launch_seed(bool, const Db &, const Index &, const SeedParams &, hipStream_t);
-void launch_seed_big(bool, const Db &, const Index &, const SeedParams &, uint32_t, hipStream_t);
-void launch_rs_range(const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
-void launch_dust(bool, uint64_t, uint64_t, const uint64_t *, const uint64_t *, const uint64_t *, const TxInfo *, uint32_t, int,
-                 int, int, uint32_t *, uint64_t *, uint32_t, uint64_t *, hipStream_t);
-uint32_t dust_scratch_words(uint32_t);
-uint64_t dust_event_words(uint32_t);
-void launch_extend_rows(bool, const Db &, const ExtParams &, hipStream_t);
-void launch_extend_retry(bool, const Db &, const ExtParams &, hipStream_t);
-void launch_later_rounds(bool, const Db &, const ExtParams &, bool, const LaterParams &, Cand *const[2],
-                         uint32_t *const[2], int32_t *const[2], uint32_t *const[2], unsigned long long *, hipStream_t);
-void launch_later_finish(const ExtParams &, const LaterParams &, hipStream_t);
-int row_slot_words_max(bool amb);
-void launch_group(const GroupParams &, int, hipStream_t);
-
-void launch_rbh(const RbhParams &, int, hipStream_t);
-void launch_hkey(const DHsp *h, uint64_t n, const uint32_t *tx_gene, HKey *out, hipStream_t st);
-void launch_rbh_place(const RbhParams &, hipStream_t);
-void launch_gather_rows(const DHsp *, const DRow *, uint64_t, DHsp *, hipStream_t);
-void launch_cc(const DEdge *, uint64_t, uint32_t, const int32_t *, int, int, uint32_t *, uint32_t *, uint32_t *,
-               uint32_t *, uint32_t *, uint8_t *, unsigned long long *, hipStream_t);
-void launch_pair_sums(const DEdge *, uint64_t, const uint32_t *, const uint8_t *, unsigned long long *,
-                      unsigned long long *, unsigned long long *, unsigned long long *, hipStream_t);
-void launch_distance(const unsigned long long *, const unsigned long long *, const int32_t *, const int32_t *,
-                     int, int, double *, unsigned int *, hipStream_t);
-// components.hip
-void launch_comp_keys(const uint32_t *, const uint32_t *, const uint8_t *, const uint32_t *, uint32_t, uint64_t *,
-                      unsigned long long *, hipStream_t);
-void launch_comp_members(const uint64_t *, uint64_t, uint32_t, uint32_t *, unsigned long long *, hipStream_t);
-void launch_comp_sums(const DEdge *, uint64_t, const uint32_t *, const uint8_t *, const uint32_t *, uint64_t,
-                      unsigned long long *, unsigned long long *, hipStream_t);
-void launch_comp_pack(const unsigned long long *, const unsigned long long *, uint64_t, uint2 *, unsigned long long *,
-                      hipStream_t);
-bool launch_resample(const uint2 *, const uint16_t *, uint64_t, uint64_t, uint32_t, unsigned long long *,
-                     unsigned long long *, hipStream_t);
-void launch_resample_distance(const unsigned long long *, const unsigned long long *, const int32_t *, const int32_t *,
-                              int, int, uint64_t, uint64_t, double *, unsigned int *, hipStream_t);
-// nj.hip
-size_t nj_lds_bytes(bool, int, int);
-hipError_t launch_nj(bool, const double *, int, int, int, double *, uint64_t *, int32_t *, double *, uint64_t *,
-                     uint8_t *, hipStream_t);
-void launch_nj_support(const uint64_t *, int, const uint64_t *, const uint8_t *, int, int, int, uint32_t *, uint32_t *,
-                       hipStream_t);
-}  // namespace rcg
-
-using namespace rcg;
+// Owns the device buffers and drives the kernels of kernels.hip on one HIP
+// stream, from rc_create to the finished graph phase. What a caller reads out
+// of a finished engine is in results.hip (converted back to reference
+// semantics: 1-based BLAST coordinates, pandas index labels, sorted-label
+// matrix order) and analysis.hip.
+#include "engine.h"
 
 static thread_local std::string g_err;
-static const size_t FRONT_PAD = 2;   // zero words in front of every packed array
 
-static int fail(int code, const std::string &msg)
+int rcg_fail(int code, const std::string &msg)
 {
     g_err = msg;
     return code;
 }
 
-int rcg_fail(int code, const std::string &msg)
-{
-    return fail(code, msg);
-}
-
-#define HIPCHK(x)                                                                                    \
-    do {                                                                                             \
-        hipError_t e_ = (x);                                                                         \
-        if (e_ != hipSuccess) return fail(RC_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define CHK(x)                  \
-    do {                        \
-        int r_ = (x);           \
-        if (r_ != RC_OK) return r_; \
-    } while (0)
-
 // Device bytes the engines of this process hold (now and at most), for the
 // HBM footprint checks (rc_timing.dev_bytes / dev_peak_bytes)
 static std::atomic<long long> g_dev_bytes{0}, g_dev_peak{0};
-static void dev_account(long long b)
+void dev_account(long long b)
 {
     const long long v = g_dev_bytes.fetch_add(b) + b;
     long long pk = g_dev_peak.load();
     while (v > pk && !g_dev_peak.compare_exchange_weak(pk, v)) {
     }
 }
-
-// Device buffer that only grows (no allocation once sized: reruns are alloc-free).
-template <class T>
-struct DBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap && p) return RC_OK;
-        release();
-        size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        if (hipMalloc((void **)&p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail(RC_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-        }
-        cap = std::max<size_t>(n, 1);
-        dev_account((long long)(cap * sizeof(T)));
-        return RC_OK;
-    }
-    // a buffer allocated elsewhere (the growth paths that keep contents)
-    void adopt(T *np, size_t ncap)
-    {
-        dev_account((long long)(ncap * sizeof(T)));   // both are held until the old one goes
-        T *op = p;
-        const size_t oc = cap;
-        p = np;
-        cap = ncap;
-        if (op) {
-            (void)hipFree(op);
-            dev_account(-(long long)(oc * sizeof(T)));
-        }
-    }
-    ~DBuf() { release(); }
-    void release()
-    {
-        if (p) {
-            (void)hipFree(p);
-            dev_account(-(long long)(cap * sizeof(T)));
-        }
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 // every byte is A/C/G/T in either case (a branch-free inner loop the compiler
 // vectorises; the scan stops at the first 64 KiB block holding another byte)
@@ -222,7 +46,6 @@ static bool all_acgt(const char *s, uint64_t n)
 // Karlin-Altschul statistics (BLAST restated; same spec as the oracle)
 // ------------------------------------------------------------------------
 namespace stats {
-const double LAMBDA = 1.28, K = 0.46, ALPHA = 1.5, BETA = -2.0;
 
 // BLAST_ComputeLengthAdjustment
 int32_t length_adjustment(double m, double n, double N)
@@ -305,40 +128,6 @@ int32_t bits10(int32_t score_half)
 // engine
 // ------------------------------------------------------------------------
 
-struct SampleRec {
-    std::string label;
-    uint64_t base = 0, nbases = 0;   // base: position in the concatenation of all samples (host bookkeeping)
-    uint32_t tx_begin = 0, n_tx = 0;
-    uint32_t gene_begin = 0, n_genes = 0;
-    bool resident = true;            // bases on this GPU (rc_add_sample with a sequence)
-    uint64_t abase = 0;              // resident: offset in d_ascii (a multiple of TILE_ALIGN)
-};
-
-// Samples start at multiples of TILE_ALIGN bases in d_ascii and in a tile's
-// packed arrays: a 2^POS_TX_SHIFT-base block of the position -> transcript
-// table never spans two samples, whatever samples a tile holds.
-static const uint64_t TILE_ALIGN = 1ull << POS_TX_SHIFT;
-static uint64_t align_up(uint64_t x) { return (x + TILE_ALIGN - 1) & ~(TILE_ALIGN - 1); }
-
-// Test hooks: every one is set by a GPU test to reach a path that the default
-// takes only at full size. The environment is read once, when the engine is
-// created (rc_create); a variable changed later does not reach an engine that
-// exists. One line per variable: name (default) and meaning.
-struct Knobs {
-    bool share;           // RC_SHARE (1): 0 = a pair's two directed searches one after the other
-    uint64_t tile_bases;  // RC_TILE_BASES (2^32 - 2^24; at least TILE_ALIGN): a tile's most bases (tests: small tiles)
-    bool tile_split;      // RC_TILE_SPLIT (1): 0 = no split tiles, so no index reuse from tile to tile
-    int ovf_cap0;         // RC_OVF_CAP0 (unset = 0; else at least 1): first HSP overflow buffer size (tests: its retry)
-    int win_words;        // RC_WIN_WORDS (unset = 0; else at least 4): row staging windows of that many words (tests)
-    bool later;           // RC_LATER (1): 0 = extend_kernel runs the deferred searches' later seeds whole
-    int later_rows;       // RC_LATER_ROWS (64): 32 = the later-seed rounds run the 32-lane pass first
-    uint64_t later_cap;   // RC_LATER_CAP (24 M, at least 1): searches the later-seed rounds hold states for
-    bool rbh_two_pass;    // RC_RBH_TWO_PASS (unset; any value sets it): always the full second RBH pass
-    int resume;           // RC_RESUME (unset = -1: by the last run's overflows): 1 = always save 32-lane states, 0 = never
-    uint32_t index_cap;   // RC_INDEX_CAP (unset = 0: the local sort's capacity; else at least 2): main-index ranges of more keys count as oversized (tests: the fallbacks)
-    int nj_lds;           // RC_NJ_LDS (128; at most 128): the most samples whose neighbour-joining matrix lives in LDS; 0 = every tree through the global workspace (tests: that path)
-};
-
 static Knobs read_knobs()
 {
     const auto env = [](const char *name) -> const char * { return getenv(name); };
@@ -358,233 +147,6 @@ static Knobs read_knobs()
     k.index_cap = env("RC_INDEX_CAP") ? (uint32_t)std::max(2, num("RC_INDEX_CAP", 2)) : 0u;
     k.nj_lds = std::min(128, std::max(0, num("RC_NJ_LDS", 128)));
     return k;
-}
-
-struct rc_engine {
-    rc_opts o{};
-    Knobs knobs{};
-    hipStream_t st = nullptr;
-    hipStream_t st2 = nullptr;   // DUST beside the index build
-    std::vector<SampleRec> samples;
-    uint64_t total_bases = 0;   // input bases added so far (all samples)
-    uint64_t ascii_used = 0;    // bytes of d_ascii in use (resident samples, TILE_ALIGN-aligned)
-    std::vector<uint64_t> tx_start{0};
-    std::vector<int32_t> tx_sample, tx_gene_id, tx_iso;
-    bool has_amb = false;
-
-    // derived on upload
-    std::vector<uint32_t> tx_gene, gene_tx_off, gene_tx, sample_gene_begin, sample_tx_begin;
-    std::vector<int32_t> gene_sample, gene_id;
-    std::vector<int64_t> db_len, db_n;
-    std::vector<int32_t> pair_a, pair_b, pair_index;
-    std::vector<int64_t> shard_first;   // shard r owns pairs [shard_first[r], shard_first[r + 1])
-    std::vector<uint32_t> pair_item_begin;
-    int32_t max_len = 0;
-    int xbits = 24;                     // seed-key position bits (pos_bits(max_len))
-    uint64_t n_items = 0;
-    int index_bits = 16;
-    uint64_t n_index = 0;               // entries of the loaded tile's index
-    uint64_t tile_npos = 0;             // 16-mer positions of the loaded tile's indexed transcripts
-    std::vector<TxInfo> h_tx;           // every transcript (start 0: the device table holds tile starts)
-    std::vector<uint64_t> sample_kmers; // 16-mer positions of each sample's transcripts
-    std::vector<TileSeg> h_segs;        // the loaded tile's samples (load_tile)
-    std::vector<uint64_t> h_spos, h_send;
-
-    // tiles of this shard (plan_tiles) and the one whose tables are loaded
-    struct Tile {
-        std::vector<int> samples;                 // ascending
-        std::vector<std::pair<int, int>> pairs;   // (a, b), a < b
-        // split tiles (a shard cut into several, every a below every b):
-        // the b chunk's samples sit at bstart, the same in every tile of that
-        // chunk, so consecutive tiles of one b chunk share its 16-mer index
-        // and its DUST masks (only the a part is redone)
-        int bchunk = -1;
-        uint64_t bstart = 0;
-    };
-    std::vector<Tile> tiles;
-    int64_t tiles_for = -1;
-    int tile_loaded = -1;
-    std::vector<uint64_t> tile_pos;     // first base of each sample in the loaded tile
-    uint64_t tile_total = 0;
-    bool tile_direct = false;           // the loaded tile is d_ascii's layout (no gathered copy)
-    uint32_t tile_ntx = 0;              // the tile's transcripts (DUST, near-mask index)
-    uint32_t tile_nitx = 0;             // ... of its subject samples (the 16-mer index)
-    std::vector<uint32_t> tile_tx_first;   // first transcript (in d_tile_tx) of each sample of the tile
-    // DUST masks given by rc_set_dust_masks (computed once per sample across
-    // shards): word offset of each sample's mask in d_dust_imp, ~0 = not given
-    std::vector<uint64_t> dust_imp_off;
-    // after an rc_dust_masks pass over the loaded tile itself: which samples'
-    // masks it recomputed (the others were cleared); empty = every tile sample
-    std::vector<char> dmask_only;
-    // the b chunk (split tiles) whose index and DUST masks the device holds
-    // from this run's previous tile (-1: none)
-    int idx_bchunk = -1;
-    uint64_t idx_bstart = 0;
-    uint64_t hsp_used = 0;              // HSPs appended to d_hsp by the tiles of this run
-
-    // external HSPs
-    bool external = false;
-    std::map<std::pair<int, int>, std::vector<rc_hsp>> ext;
-
-    // state
-    bool uploaded = false, aligned = false, finished = false;
-    // this shard's sample pairs [pair0, pair1) and their items [item0, item1)
-    uint64_t pair0 = 0, pair1 = 0, item0 = 0, item1 = 0;
-    uint64_t n_local_edges = 0;
-    bool rbh_done = false;
-    bool graph_only = false;        // an imported graph + tables, no alignment (rc_import_edges on a fresh engine)
-    int32_t sample_count_given = 0; // > 0: the ideal test's sample count (rc_set_sample_count)
-
-    // device buffers
-    DBuf<uint8_t> d_ascii, d_tile_ascii;
-    DBuf<TxInfo> d_tile_tx, d_tile_itx;
-    DBuf<uint32_t> d_tile_gid;          // global id of each tile transcript
-    DBuf<TileSeg> d_tile_segs;
-    DBuf<uint64_t> d_tile_send, d_tx_rel, d_kpre;   // tile sample ends; per transcript: start in its sample,
-                                                    // 16-mer slots of its sample's transcripts before it
-    DBuf<uint64_t> d_F, d_RC, d_AF, d_ARC;
-    DBuf<TxInfo> d_tx;
-    DBuf<IsoRec> d_giso;
-    DBuf<uint32_t> d_tx_gene, d_gene_tx_off, d_gene_tx, d_sample_gene_begin, d_sample_tx_begin;
-    DBuf<int32_t> d_gene_sample;
-    DBuf<uint64_t> d_kpos_off, d_kcnt;
-    // shared searches with DUST: masked tile transcripts, the near-mask index
-    // of the reverse pass, its reverse-only seeds (sorted by forward gene)
-    DBuf<uint8_t> d_tile_masked;
-    DBuf<uint64_t> d_ment, d_ment2;
-    DBuf<uint32_t> d_mbucket;
-    int mindex_bits = 16;
-    uint64_t n_mindex = 0, mnear_cap = 0;
-    DBuf<LSeed> d_rseeds;
-    DBuf<uint32_t> d_rseed_gene, d_rs_key, d_rs_idx, d_rs_range;
-    DBuf<unsigned long long> d_rctr;   // [0] near-index entries, [1] reverse-only seeds
-    DBuf<uint64_t> d_rtmask;
-    DBuf<int32_t> d_trange, d_rtrange;   // [N][2] subject-sample range of each query sample (tmask / rtmask)
-    uint64_t rseed_cap = 0, n_rseeds = 0;
-    uint32_t res_cap = 0;
-    // fraction of the last run's candidates whose first-seed extension
-    // outgrew the 32-lane window (selects the saving row kernel, RC_RESUME)
-    double ovf_frac = 0.0;
-    DBuf<uint64_t> d_ent, d_ent2;   // (k-mer << 32 | position), unsorted / sorted
-    // the index sort's scratch (sort.hip): digit histograms + tile counters,
-    // the look-back table (zeroed when allocated; tagged by pass epoch)
-    DBuf<uint32_t> d_sort_scratch;
-    DBuf<uint64_t> d_sort_status;
-    uint32_t sort_epoch = 0;
-    // the main index's range offsets (2^G + 1) and its list of oversized ranges
-    DBuf<uint32_t> d_range_off, d_range_list;
-    DBuf<uint32_t> d_bucket;
-    DBuf<PosTx> d_pos_tx;
-    DBuf<uint64_t> d_sample_pos, d_txstart, d_kpos_rel, d_dmask, d_dust_imp;
-    DBuf<uint32_t> d_dust_scratch;
-    DBuf<uint64_t> d_dust_events;
-    DBuf<unsigned long long> d_prof;
-    DBuf<uint8_t> d_tmp;
-    DBuf<int32_t> d_thr, d_bits10;
-    DBuf<DHsp> d_hsp;
-    DBuf<HKey> d_hkey;   // RBH: (bit score, subject gene) per d_hsp entry
-    DBuf<GSeed> d_seeds;
-    DBuf<Cand> d_cands;
-    DBuf<DHsp> d_cand_hsp, d_ovf;
-    DBuf<uint8_t> d_cand_nh;
-    DBuf<int32_t> d_cand_box, d_cand_box2;
-    // shared searches (RC_SHARE, default): the reverse search's HSPs per candidate
-    DBuf<DHsp> d_cand_hsp_r;
-    DBuf<uint8_t> d_cand_nh_r;
-    DBuf<uint32_t> d_cand_ovf_r, d_defer_r, d_list2, d_wide0, d_wide1;
-    DBuf<int32_t> d_resume;   // saved 32-lane extension states for the 64-lane pass (RES_REC ints each)
-    // later-seed rounds (shared searches): search states, the rounds' work
-    // (alternating), active lists, counters
-    DBuf<int32_t> d_later, d_lbox0, d_lbox1;
-    DBuf<Cand> d_lvc0, d_lvc1;
-    DBuf<uint32_t> d_llist0, d_llist1, d_lact0, d_lact1, d_lfull0, d_lfull1;
-    DBuf<unsigned long long> d_lcnt;
-    // both directed searches of a pair from one candidate set (query = the
-    // lower sample), unless spec 5b or RC_SHARE=0 (one after
-    // the other); fixed when the engine is created
-    bool share = false;
-    DBuf<DRow> d_rows_tmp;
-    DBuf<DEdge> d_edges_tmp;
-    DBuf<uint32_t> d_cand_ovf, d_gc_off, d_gc_cnt, d_gcount, d_defer;
-    DBuf<uint64_t> d_gscan, d_mscan, d_mkey, d_tmask, d_mbig;
-    DBuf<uint32_t> d_mcnt, d_mcur, d_tx_pos, d_iso_pre, d_iso_list, d_iso_list_r;
-    DBuf<unsigned long long> d_shard_cnt, d_shard_prefix;
-    uint64_t seed_cap = 0, cand_cap = 0, ovf_cap = 0;   // per-shard / total capacities
-    // (gene, sample) seed passes too big for LDS, and their global scratch
-    DBuf<uint64_t> d_big_out, d_big_list, d_big_retry;
-    DBuf<LSeed> d_big_seeds;
-    DBuf<uint32_t> d_big_seg;
-    DBuf<uint8_t> d_big_segT;
-    uint64_t big_list_cap = 1 << 16;
-    uint32_t big_cap = 1 << 13;
-    DBuf<uint32_t> d_grp_off, d_grp_cnt;
-    DBuf<unsigned long long> d_count;
-    DBuf<unsigned int> d_status;
-    DBuf<uint32_t> d_pair_item_begin;
-    DBuf<int32_t> d_pair_a, d_pair_b, d_pair_index;
-    DBuf<uint32_t> d_cnt4;   // 4 * (n_items + 1)
-    DBuf<uint64_t> d_off4;   // 4 * (n_items + 1)
-    DBuf<DRow> d_rows;
-    DBuf<DHsp> d_gather;
-    DBuf<DEdge> d_edges;
-    uint64_t n_rows = 0, n_edges = 0, n_hsps = 0, n_seeds = 0, n_cands = 0;
-    DBuf<uint32_t> d_parent, d_present, d_cnodes, d_cedges, d_sample_present;
-    DBuf<uint8_t> d_ideal;
-    DBuf<unsigned long long> d_stats, d_num, d_den, d_num_all, d_den_all;
-    DBuf<int32_t> d_order;
-    DBuf<double> d_dist;
-    // per-component tables (components.hip), built by the first call that
-    // needs them after a graph phase and dropped by the next one: rank of each
-    // gene's ideal[] prefix, members [C][S], sums [C][P] and their 32-bit copy
-    bool comp_valid = false;
-    uint64_t comp_n = 0, comp_max_cell = 0;
-    uint32_t comp_S = 0;
-    DBuf<uint32_t> d_crank, d_cmember;
-    DBuf<unsigned long long> d_cnum, d_cden, d_cstat, d_rnum, d_rden;
-    DBuf<uint2> d_ccell;
-    DBuf<uint16_t> d_rweight;
-    // neighbour joining (nj.hip): input matrices of rc_nj, the trees, the
-    // reference splits with their support (n_ref counters, then n_valid) and
-    // the workspace of the trees too large for LDS
-    DBuf<double> d_nj_in, d_nj_len, d_nj_wsm;
-    DBuf<int32_t> d_nj_joins;
-    DBuf<uint64_t> d_nj_splits, d_nj_ref, d_nj_wsmask;
-    DBuf<uint8_t> d_nj_valid;
-    DBuf<uint32_t> d_nj_sup;
-
-    // host results
-    std::vector<unsigned long long> h_num, h_den, h_num_all, h_den_all, h_stats;
-    std::vector<double> h_ss;   // search space of a query of length L against sample T: [T][L]
-    std::vector<double> h_exp;  // exp(-lambda * S / 2) per raw score in half units S (stats::evalue's factor)
-    rc_timing tm{};
-    hipEvent_t ev[16] = {};
-    hipEvent_t evd[3] = {};   // DUST start / end on st2, its start condition on st
-
-    ~rc_engine()
-    {
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t x : evd)
-            if (x) (void)hipEventDestroy(x);
-        if (st2) (void)hipStreamDestroy(st2);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
-static int set_device(rc_engine *e) { HIPCHK(hipSetDevice(e->o.device)); return RC_OK; }
-
-static double wall_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// the alignment's blocking waits on the engine's stream (rc_timing.host_wait_ms)
-static int wait_st(rc_engine *e)
-{
-    const double t0 = wall_ms();
-    HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.host_wait_ms += wall_ms() - t0;
-    return RC_OK;
 }
 
 extern "C" {
@@ -1026,16 +588,6 @@ static int upload(rc_engine *e)
     e->tile_loaded = -1;
     e->uploaded = true;
     return RC_OK;
-}
-
-static double ev_ms(rc_engine *e, int a, int b)
-{
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, e->ev[a], e->ev[b]) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return ms;
 }
 
 // ------------------------------------------------------------------------
@@ -2658,39 +2210,6 @@ static int do_finish(rc_engine *e)
     return RC_OK;
 }
 
-// ------------------------------------------------------------------------
-// results
-// ------------------------------------------------------------------------
-
-static rc_hsp to_rc_hsp(const rc_engine *e, const DHsp &d, int qs_, int ss_)
-{
-    rc_hsp h;
-    h.q_tx = d.q_tx - e->samples[qs_].tx_begin;
-    h.s_tx = d.s_tx - e->samples[ss_].tx_begin;
-    h.qstart = d.qstart; h.qend = d.qend; h.sstart = d.sstart; h.send = d.send;
-    h.length = d.length; h.nident = d.nident; h.mismatch = d.mismatch; h.gaps = d.gaps;
-    h.gapopen = d.gapopen; h.score_half = d.score_half; h.bits10 = d.bits10; h.strand = d.strand & 1;
-    const int64_t qlen = (int64_t)(e->tx_start[d.q_tx + 1] - e->tx_start[d.q_tx]);
-    const double ss = qlen <= e->max_len ? e->h_ss[(size_t)ss_ * (e->max_len + 1) + (size_t)qlen]
-                                         : stats::search_space(qlen, e->db_len[ss_], e->db_n[ss_]);
-    // stats::evalue, its exp() taken from the table (the same product, in
-    // the same order: bit-identical)
-    h.evalue = d.score_half >= 0 && (size_t)d.score_half < e->h_exp.size() ? ss * stats::K * e->h_exp[d.score_half]
-                                                                            : stats::evalue(ss, d.score_half);
-    return h;
-}
-
-static int copy_groups(rc_engine *e, std::vector<uint32_t> &off, std::vector<uint32_t> &cnt)
-{
-    const size_t n = (size_t)e->gene_sample.size() * e->samples.size();
-    off.resize(n);
-    cnt.resize(n);
-    if (!n) return RC_OK;
-    HIPCHK(hipMemcpy(off.data(), e->d_grp_off.p, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cnt.data(), e->d_grp_cnt.p, n * 4, hipMemcpyDeviceToHost));
-    return RC_OK;
-}
-
 extern "C" {
 
 int rc_upload(rc_engine *e)
@@ -2726,649 +2245,6 @@ int rc_set_sample_count(rc_engine *e, int32_t sample_count)
     e->sample_count_given = sample_count;
     return RC_OK;
 }
-
-int rc_hsps(rc_engine *e, int32_t q, int32_t s, rc_hsp *buf, uint64_t cap, uint64_t *n)
-{
-    if (!e || !n) return fail(RC_E_ARG, "null argument");
-    if (!e->aligned) return fail(RC_E_STATE, "no alignment yet");
-    const int N = (int)e->samples.size();
-    if (q < 0 || q >= N || s < 0 || s >= N) return fail(RC_E_ARG, "bad sample");
-    CHK(set_device(e));
-    std::vector<uint32_t> off, cnt;
-    CHK(copy_groups(e, off, cnt));
-    const SampleRec &Q = e->samples[q];
-    const uint32_t ng = (uint32_t)e->gene_sample.size();
-    uint64_t tot = 0;
-    for (uint32_t g = Q.gene_begin; g < Q.gene_begin + Q.n_genes; g++) tot += cnt[grp_index(g, s, ng)];
-    *n = tot;
-    if (!buf) return RC_OK;
-    if (cap < tot) return fail(RC_E_CAPACITY, "buffer too small");
-    uint64_t w = 0;
-    std::vector<DHsp> tmp;
-    for (uint32_t g = Q.gene_begin; g < Q.gene_begin + Q.n_genes; g++) {
-        const uint32_t c = cnt[grp_index(g, s, ng)];
-        if (!c) continue;
-        tmp.resize(c);
-        HIPCHK(hipMemcpy(tmp.data(), e->d_hsp.p + off[grp_index(g, s, ng)], c * sizeof(DHsp), hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < c; i++) buf[w++] = to_rc_hsp(e, tmp[i], q, s);
-    }
-    return RC_OK;
-}
-
-// A pair's rows on the host: its table rows (DRow) and their HSPs, fetched
-// from the device (the engine's stream; one caller at a time).
-struct PairRaw {
-    int32_t s1 = 0, s2 = 0;
-    uint64_t n = 0;
-    const DRow *rows = nullptr;   // n rows and their HSPs: in the vectors, or in a pinned slab
-    const DHsp *hs = nullptr;
-    std::vector<DRow> vrows;
-    std::vector<DHsp> vhs;
-    std::shared_ptr<char> slab;   // (returned to its pool when the last holder lets go)
-};
-
-// Pinned host slabs the rows of many pairs come to by DMA (rc_write_outputs):
-// at most `cap` of them, allocated as needed, each holding `bytes`; a slab
-// goes back to the pool when its pair's last consumer drops it. Pageable
-// copies faulted fresh pages for every pair (3.6 GB at C3).
-struct SlabPool {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<char *> all, free;
-    size_t bytes = 0, cap = 0;
-    ~SlabPool()
-    {
-        for (char *p : all) (void)hipHostFree(p);
-    }
-    // a slab (blocks while all `cap` are in use); nullptr if pinning fails
-    std::shared_ptr<char> get()
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        if (free.empty() && all.size() < cap) {
-            char *p = nullptr;
-            if (hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                return nullptr;
-            }
-            all.push_back(p);
-            free.push_back(p);
-        }
-        cv.wait(lk, [&] { return !free.empty(); });
-        char *p = free.back();
-        free.pop_back();
-        return std::shared_ptr<char>(p, [this](char *q) {
-            {
-                std::lock_guard<std::mutex> g(mu);
-                free.push_back(q);
-            }
-            cv.notify_all();
-        });
-    }
-};
-
-static int pair_row_range(rc_engine *e, int32_t s1, int32_t s2, uint64_t &r0, uint64_t &r1)
-{
-    if (!e->rbh_done || e->graph_only) return fail(RC_E_STATE, "no gene matches tables on this engine");
-    const int N = (int)e->samples.size();
-    if (s1 < 0 || s1 >= N || s2 < 0 || s2 >= N || s1 >= s2) return fail(RC_E_ARG, "need s1 < s2 (input order)");
-    CHK(set_device(e));
-    const uint64_t p = (uint64_t)e->pair_index[s1 * N + s2];
-    if (p < e->pair0 || p >= e->pair1) return fail(RC_E_ARG, "pair belongs to another shard");
-    const uint64_t ib = e->pair_item_begin[p] - e->item0, ie = e->pair_item_begin[p + 1] - e->item0;
-    HIPCHK(hipMemcpy(&r0, e->d_off4.p + ib, 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&r1, e->d_off4.p + ie, 8, hipMemcpyDeviceToHost));
-    return RC_OK;
-}
-
-// a pair's rows and their HSPs to the host: into `pool`'s pinned slabs when
-// given and big enough, else into the PairRaw's own vectors
-static int fetch_pair(rc_engine *e, int32_t s1, int32_t s2, PairRaw &out, SlabPool *pool = nullptr,
-                      const uint64_t *range = nullptr)
-{
-    uint64_t r0 = 0, r1 = 0;
-    if (range) {
-        r0 = range[0];
-        r1 = range[1];
-    } else {
-        CHK(pair_row_range(e, s1, s2, r0, r1));
-    }
-    const uint64_t nr = r1 - r0;
-    out.s1 = s1;
-    out.s2 = s2;
-    out.n = nr;
-    if (!nr) return RC_OK;
-    CHK(e->d_gather.ensure(nr));
-    launch_gather_rows(e->d_hsp.p, e->d_rows.p + r0, nr, e->d_gather.p, e->st);
-    HIPCHK(hipGetLastError());
-    DRow *rows = nullptr;
-    DHsp *hs = nullptr;
-    if (pool && nr * (sizeof(DRow) + sizeof(DHsp)) <= pool->bytes) out.slab = pool->get();
-    if (out.slab) {
-        hs = reinterpret_cast<DHsp *>(out.slab.get());
-        rows = reinterpret_cast<DRow *>(out.slab.get() + nr * sizeof(DHsp));
-    } else {
-        out.vrows.resize(nr);
-        out.vhs.resize(nr);
-        rows = out.vrows.data();
-        hs = out.vhs.data();
-    }
-    HIPCHK(hipMemcpyAsync(rows, e->d_rows.p + r0, nr * sizeof(DRow), hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(hs, e->d_gather.p, nr * sizeof(DHsp), hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
-    out.rows = rows;
-    out.hs = hs;
-    return RC_OK;
-}
-
-// rc_row records of fetched rows (host only: thread-safe, the engine's host
-// tables are read only)
-static void convert_rows(const rc_engine *e, const PairRaw &raw, rc_row *buf)
-{
-    const int32_t s1 = raw.s1, s2 = raw.s2;
-    const uint64_t nr = raw.n;
-    const DRow *rows = raw.rows;
-    const DHsp *hs = raw.hs;
-    for (uint64_t i = 0; i < nr; i++) {
-        const DHsp &d = hs[i];
-        rc_row &r = buf[i];
-        const bool rev = rows[i].reverse != 0;
-        // forward rows: query in s2, subject in s1; reverse rows the other way round
-        const int qs_ = rev ? s1 : s2, ss_ = rev ? s2 : s1;
-        r.hsp = to_rc_hsp(e, d, qs_, ss_);
-        const uint32_t tq = rev ? d.s_tx : d.q_tx;   // transcript of s2 (qgene side)
-        const uint32_t ts = rev ? d.q_tx : d.s_tx;   // transcript of s1 (sgene side)
-        r.qgene = e->tx_gene_id[tq];
-        r.qiso = e->tx_iso[tq];
-        r.sgene = e->tx_gene_id[ts];
-        r.siso = e->tx_iso[ts];
-        r.q_tx = tq - e->samples[s2].tx_begin;
-        r.s_tx = ts - e->samples[s1].tx_begin;
-        r.reverse = rev ? 1 : 0;
-        r.label = rows[i].label;
-    }
-}
-
-int rc_pair_rows(rc_engine *e, int32_t s1, int32_t s2, rc_row *buf, uint64_t cap, uint64_t *n)
-{
-    if (!e || !n) return fail(RC_E_ARG, "null argument");
-    uint64_t r0 = 0, r1 = 0;
-    CHK(pair_row_range(e, s1, s2, r0, r1));
-    *n = r1 - r0;
-    if (!buf) return RC_OK;
-    if (cap < r1 - r0) return fail(RC_E_CAPACITY, "buffer too small");
-    if (r1 == r0) return RC_OK;
-    PairRaw raw;
-    CHK(fetch_pair(e, s1, s2, raw));
-    convert_rows(e, raw, buf);
-    return RC_OK;
-}
-
-int rc_graph_stats(rc_engine *e, rc_stats *s)
-{
-    if (!e || !s) return fail(RC_E_ARG, "null argument");
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    s->components = (int64_t)e->h_stats[0];
-    s->ideal_components = (int64_t)e->h_stats[1];
-    s->ideal_nodes = (int64_t)e->h_stats[2];
-    s->nodes = (int64_t)e->h_stats[3];
-    s->sample_count = (int32_t)e->h_stats[4];
-    s->pad = 0;
-    s->edges = (int64_t)e->n_edges;
-    s->hsps = (int64_t)e->n_hsps;
-    s->seeds = (int64_t)e->n_seeds;
-    s->candidates = (int64_t)e->n_cands;
-    s->table_rows = (int64_t)e->n_rows;
-    return RC_OK;
-}
-
-int rc_edges(rc_engine *e, rc_edge *buf, uint64_t cap, uint64_t *n)
-{
-    if (!e || !n) return fail(RC_E_ARG, "null argument");
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    *n = e->n_edges;
-    if (!buf) return RC_OK;
-    if (cap < e->n_edges) return fail(RC_E_CAPACITY, "buffer too small");
-    CHK(set_device(e));
-    std::vector<DEdge> ed(e->n_edges);
-    if (!ed.empty()) HIPCHK(hipMemcpy(ed.data(), e->d_edges.p, ed.size() * sizeof(DEdge), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < ed.size(); i++) {
-        buf[i].sample_a = e->gene_sample[ed[i].a];
-        buf[i].gene_a = e->gene_id[ed[i].a];
-        buf[i].sample_b = e->gene_sample[ed[i].b];
-        buf[i].gene_b = e->gene_id[ed[i].b];
-    }
-    return RC_OK;
-}
-
-int rc_ideal_nodes(rc_engine *e, int32_t *sample, int32_t *gene, uint64_t cap, uint64_t *n)
-{
-    if (!e || !n) return fail(RC_E_ARG, "null argument");
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    CHK(set_device(e));
-    const uint32_t ng = (uint32_t)e->gene_sample.size();
-    std::vector<uint32_t> parent(ng), present(ng);
-    std::vector<uint8_t> ideal(ng);
-    if (ng) {
-        HIPCHK(hipMemcpy(parent.data(), e->d_parent.p, ng * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(present.data(), e->d_present.p, ng * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ideal.data(), e->d_ideal.p, ng, hipMemcpyDeviceToHost));
-    }
-    uint64_t c = 0;
-    for (uint32_t v = 0; v < ng; v++)
-        if (present[v] && ideal[parent[v]]) {
-            if (sample && gene) {
-                if (c >= cap) return fail(RC_E_CAPACITY, "buffer too small");
-                sample[c] = e->gene_sample[v];
-                gene[c] = e->gene_id[v];
-            }
-            c++;
-        }
-    *n = c;
-    return RC_OK;
-}
-
-int rc_pair_sums(rc_engine *e, int64_t *num, int64_t *den)
-{
-    if (!e || !num || !den) return fail(RC_E_ARG, "null argument");
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    const int N = (int)e->samples.size();
-    for (int a = 0; a < N; a++)
-        for (int b = 0; b < N; b++) {
-            if (a == b) {
-                num[a * N + b] = den[a * N + b] = 0;
-                continue;
-            }
-            const int p = e->pair_index[a * N + b];
-            num[a * N + b] = (int64_t)e->h_num[p];
-            den[a * N + b] = (int64_t)e->h_den[p];
-        }
-    return RC_OK;
-}
-
-// Unfiltered sums: every gene matches table row of the pair
-// (UnfilteredSimilarity, unfiltered_distance.py:9-16 over similarities_from_dfs,
-// similarity_computer.py:21-42).
-int rc_pair_sums_unfiltered(rc_engine *e, int64_t *num, int64_t *den)
-{
-    if (!e || !num || !den) return fail(RC_E_ARG, "null argument");
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    const int N = (int)e->samples.size();
-    for (int a = 0; a < N; a++)
-        for (int b = 0; b < N; b++) {
-            if (a == b) {
-                num[a * N + b] = den[a * N + b] = 0;
-                continue;
-            }
-            const int p = e->pair_index[a * N + b];
-            num[a * N + b] = (int64_t)e->h_num_all[p];
-            den[a * N + b] = (int64_t)e->h_den_all[p];
-        }
-    return RC_OK;
-}
-
-int rc_distance_subset(rc_engine *e, const int32_t *order, int32_t n, double *out)
-{
-    if (!e || (n && (!order || !out))) return fail(RC_E_ARG, "null argument");
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    const int N = (int)e->samples.size();
-    if (n < 0 || n > N) return fail(RC_E_ARG, "bad sample count");
-    std::vector<int> seen(N, 0);
-    for (int i = 0; i < n; i++) {
-        if (order[i] < 0 || order[i] >= N || seen[order[i]]) return fail(RC_E_ARG, "order must hold distinct sample ids");
-        seen[order[i]] = 1;
-    }
-    if (!n) return RC_OK;
-    CHK(set_device(e));
-    CHK(e->d_order.ensure(n));
-    CHK(e->d_dist.ensure((size_t)n * n));
-    HIPCHK(hipMemcpyAsync(e->d_order.p, order, n * 4, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemsetAsync(e->d_status.p, 0, 4 * sizeof(unsigned int), e->st));
-    launch_distance(e->d_num.p, e->d_den.p, e->d_pair_index.p, e->d_order.p, N, n, e->d_dist.p, e->d_status.p,
-                    e->st);
-    HIPCHK(hipGetLastError());
-    unsigned int status = 0;
-    HIPCHK(hipMemcpyAsync(out, e->d_dist.p, (size_t)n * n * 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(&status, e->d_status.p, 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
-    if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
-    return RC_OK;
-}
-
-int rc_distance(rc_engine *e, const int32_t *order, double *out)
-{
-    if (!e) return fail(RC_E_ARG, "null argument");
-    return rc_distance_subset(e, order, (int32_t)e->samples.size(), out);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------
-// per-component tables and resampling (kernels: components.hip)
-// ------------------------------------------------------------------------
-
-enum { CS_MEMBERS = 0, CS_MAXCELL = 1, CS_BAD = 2, CS_N = 4 };   // slots of d_cstat
-
-// The tables of the finished graph phase, built once per graph: ranks (the
-// exclusive scan of d_ideal), members, sums, their packed copy and the largest
-// cell. They stay on the device until the next do_graph.
-static int build_components(rc_engine *e)
-{
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    if (e->comp_valid) return RC_OK;
-    CHK(set_device(e));
-    const uint32_t ng = (uint32_t)e->gene_sample.size();
-    const uint64_t P = e->pair_a.size();
-    const uint64_t S = e->h_stats[4];
-    uint64_t C = 0;
-    CHK(e->d_crank.ensure(ng));
-    CHK(e->d_cstat.ensure(CS_N));
-    HIPCHK(hipMemsetAsync(e->d_cstat.p, 0, CS_N * sizeof(unsigned long long), e->st));
-    if (ng) {
-        size_t tmp = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->d_ideal.p, e->d_crank.p, 0u, (size_t)ng,
-                                       rocprim::plus<uint32_t>(), e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::exclusive_scan(e->d_tmp.p, tmp, e->d_ideal.p, e->d_crank.p, 0u, (size_t)ng,
-                                       rocprim::plus<uint32_t>(), e->st));
-        uint32_t last_rank = 0;
-        uint8_t last_ideal = 0;
-        HIPCHK(hipMemcpyAsync(&last_rank, e->d_crank.p + ng - 1, 4, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(&last_ideal, e->d_ideal.p + ng - 1, 1, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
-        C = (uint64_t)last_rank + last_ideal;
-    }
-    if (C != e->h_stats[1]) return fail(RC_E_STATE, "the ideal[] scan disagrees with the ideal component count");
-    if (C && !S) return fail(RC_E_STATE, "ideal components without a sample count");
-    // members: sort (component id, gene) keys, the members come first
-    const uint64_t nm = C * S;
-    CHK(e->d_cmember.ensure(nm));
-    if (nm) {
-        DBuf<uint64_t> k0, k1;
-        CHK(k0.ensure(ng));
-        CHK(k1.ensure(ng));
-        launch_comp_keys(e->d_parent.p, e->d_present.p, e->d_ideal.p, e->d_crank.p, ng, k0.p,
-                         e->d_cstat.p + CS_MEMBERS, e->st);
-        HIPCHK(hipGetLastError());
-        size_t tmp = 0;
-        HIPCHK(rocprim::radix_sort_keys(nullptr, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::radix_sort_keys(e->d_tmp.p, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
-        unsigned long long members = 0;
-        HIPCHK(hipMemcpyAsync(&members, e->d_cstat.p + CS_MEMBERS, 8, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
-        if (members != nm) return fail(RC_E_STATE, "ideal components do not hold sample_count members each");
-        launch_comp_members(k1.p, nm, (uint32_t)S, e->d_cmember.p, e->d_cstat.p + CS_BAD, e->st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(e->st));   // k0, k1 go out of scope
-    }
-    // sums, packed cells, largest cell
-    const uint64_t cells = C * P;
-    CHK(e->d_cnum.ensure(cells));
-    CHK(e->d_cden.ensure(cells));
-    CHK(e->d_ccell.ensure(cells));
-    if (cells) {
-        HIPCHK(hipMemsetAsync(e->d_cnum.p, 0, cells * 8, e->st));
-        HIPCHK(hipMemsetAsync(e->d_cden.p, 0, cells * 8, e->st));
-        launch_comp_sums(e->d_edges.p, e->n_edges, e->d_parent.p, e->d_ideal.p, e->d_crank.p, P, e->d_cnum.p,
-                         e->d_cden.p, e->st);
-        launch_comp_pack(e->d_cnum.p, e->d_cden.p, cells, e->d_ccell.p, e->d_cstat.p + CS_MAXCELL, e->st);
-        HIPCHK(hipGetLastError());
-    }
-    unsigned long long st[CS_N] = {};
-    HIPCHK(hipMemcpyAsync(st, e->d_cstat.p, sizeof st, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
-    if (st[CS_BAD]) return fail(RC_E_STATE, "ideal components do not hold sample_count members each");
-    e->comp_n = C;
-    e->comp_S = (uint32_t)S;
-    e->comp_max_cell = st[CS_MAXCELL];
-    e->comp_valid = true;
-    return RC_OK;
-}
-
-extern "C" {
-
-int rc_ideal_components(rc_engine *e, int32_t *sample, int32_t *gene, uint64_t cap_nodes, uint64_t *n_comp,
-                        int32_t *sample_count)
-{
-    if (!e || !n_comp || !sample_count) return fail(RC_E_ARG, "null argument");
-    CHK(build_components(e));
-    *n_comp = e->comp_n;
-    *sample_count = (int32_t)e->comp_S;
-    if (!sample && !gene) return RC_OK;
-    if (!sample || !gene) return fail(RC_E_ARG, "null argument");
-    const uint64_t nm = e->comp_n * e->comp_S;
-    if (cap_nodes < nm) return fail(RC_E_CAPACITY, "buffer too small");
-    if (!nm) return RC_OK;
-    std::vector<uint32_t> m(nm);
-    HIPCHK(hipMemcpy(m.data(), e->d_cmember.p, nm * 4, hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < nm; i++) {
-        sample[i] = e->gene_sample[m[i]];
-        gene[i] = e->gene_id[m[i]];
-    }
-    return RC_OK;
-}
-
-int rc_component_sums(rc_engine *e, int64_t *num, int64_t *den, uint64_t cap_cells, uint64_t *n_comp,
-                      uint64_t *n_pairs)
-{
-    if (!e || !n_comp || !n_pairs) return fail(RC_E_ARG, "null argument");
-    CHK(build_components(e));
-    *n_comp = e->comp_n;
-    *n_pairs = e->pair_a.size();
-    if (!num && !den) return RC_OK;
-    if (!num || !den) return fail(RC_E_ARG, "null argument");
-    const uint64_t cells = e->comp_n * e->pair_a.size();
-    if (cap_cells < cells) return fail(RC_E_CAPACITY, "buffer too small");
-    if (!cells) return RC_OK;
-    HIPCHK(hipMemcpy(num, e->d_cnum.p, cells * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(den, e->d_cden.p, cells * 8, hipMemcpyDeviceToHost));
-    return RC_OK;
-}
-
-}  // extern "C"
-
-// rc_resample up to the filled device buffers: the replicate sums in d_rnum /
-// d_rden and, with `dist`, the n_rep x n x n distances in d_dist with their
-// status word in d_status (queued on the stream, not waited for). Events
-// ev[12], ev[13].
-static int resample_fill(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
-                         int32_t n, bool dist, bool sums_paired)
-{
-    CHK(build_components(e));
-    const uint64_t C = e->comp_n, P = e->pair_a.size();
-    const int N = (int)e->samples.size();
-    if (n_comp != C) return fail(RC_E_ARG, "n_comp is not the number of ideal components");
-    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
-    if (C && !weights) return fail(RC_E_ARG, "null argument");
-    if (!sums_paired) return fail(RC_E_ARG, "num and den go together");
-    if (n < 0 || n > N || (dist && n && !order)) return fail(RC_E_ARG, "bad sample count");
-    if (dist) {
-        std::vector<int> seen(N, 0);
-        for (int i = 0; i < n; i++) {
-            if (order[i] < 0 || order[i] >= N || seen[order[i]])
-                return fail(RC_E_ARG, "order must hold distinct sample ids");
-            seen[order[i]] = 1;
-        }
-    }
-    if (e->comp_max_cell >> 32) return fail(RC_E_LIMIT, "a component sum of 2^32 or more (stacked sums-only records)");
-    const uint64_t R = (uint64_t)n_rep;
-    uint16_t maxw = 0;
-    for (uint64_t i = 0, nw = R * C; i < nw; i++) maxw = std::max(maxw, weights[i]);
-    unsigned long long maxden = 0;
-    for (unsigned long long d : e->h_den) maxden = std::max(maxden, d);
-    // max weight x largest pair denominator bounds every replicate sum
-    if (maxw && maxden >= ((1ull << 63) + maxw - 1) / maxw)
-        return fail(RC_E_LIMIT, "weights this large could overflow the 64-bit replicate sums");
-    CHK(set_device(e));
-    const uint64_t cells = R * P;
-    CHK(e->d_rweight.ensure(R * C));
-    CHK(e->d_rnum.ensure(cells));
-    CHK(e->d_rden.ensure(cells));
-    if (R * C) HIPCHK(hipMemcpyAsync(e->d_rweight.p, weights, R * C * 2, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipEventRecord(e->ev[12], e->st));
-    if (cells) {
-        HIPCHK(hipMemsetAsync(e->d_rnum.p, 0, cells * 8, e->st));
-        HIPCHK(hipMemsetAsync(e->d_rden.p, 0, cells * 8, e->st));
-        if (!launch_resample(e->d_ccell.p, e->d_rweight.p, C, P, (uint32_t)n_rep, e->d_rnum.p, e->d_rden.p, e->st))
-            return fail(RC_E_LIMIT, "n_rep x pairs beyond the resample grid");
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(e->ev[13], e->st));
-    const uint64_t nd = dist ? R * (uint64_t)n * (uint64_t)n : 0;
-    if (nd) {
-        CHK(e->d_order.ensure(n));
-        CHK(e->d_dist.ensure(nd));
-        HIPCHK(hipMemcpyAsync(e->d_order.p, order, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
-        HIPCHK(hipMemsetAsync(e->d_status.p, 0, sizeof(unsigned int), e->st));
-        launch_resample_distance(e->d_rnum.p, e->d_rden.p, e->d_pair_index.p, e->d_order.p, N, n, R, P, e->d_dist.p,
-                                 e->d_status.p, e->st);
-        HIPCHK(hipGetLastError());
-    }
-    return RC_OK;
-}
-
-extern "C" {
-
-int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
-                int32_t n, double *out, int64_t *num, int64_t *den)
-{
-    if (!e) return fail(RC_E_ARG, "null argument");
-    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, out != nullptr, (num == nullptr) == (den == nullptr)));
-    const uint64_t cells = (uint64_t)n_rep * e->pair_a.size();
-    const uint64_t nd = out ? (uint64_t)n_rep * (uint64_t)n * (uint64_t)n : 0;
-    unsigned int status = 0;
-    if (nd) {
-        HIPCHK(hipMemcpyAsync(out, e->d_dist.p, nd * 8, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(&status, e->d_status.p, 4, hipMemcpyDeviceToHost, e->st));
-    }
-    if (num && cells) {
-        HIPCHK(hipMemcpyAsync(num, e->d_rnum.p, cells * 8, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(den, e->d_rden.p, cells * 8, hipMemcpyDeviceToHost, e->st));
-    }
-    HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.resample_ms = ev_ms(e, 12, 13);
-    if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
-    return RC_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------
-// neighbour joining (nj.hip)
-// ------------------------------------------------------------------------
-
-static const int NJ_MAX_SAMPLES = 1024;
-static const uint64_t NJ_WS_BYTES = 1ull << 30;   // workspace of the trees too large for LDS
-
-// the argument checks of rc_nj / rc_resample_trees (no device work)
-static int nj_check(int32_t n_rep, int32_t n, const uint64_t *ref, int32_t n_ref, const uint32_t *support)
-{
-    if (n < 3) return fail(RC_E_ARG, "a tree needs at least 3 samples");
-    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
-    if (n > NJ_MAX_SAMPLES) return fail(RC_E_LIMIT, "more than 1024 samples in a neighbour-joining tree");
-    if (n_ref < 0 || (n_ref > 0 && !ref)) return fail(RC_E_ARG, "bad reference splits");
-    if (support && !ref) return fail(RC_E_ARG, "support needs ref_splits");
-    const int W = (n + 63) / 64;
-    for (int64_t k = 0; k < n_ref; k++) {
-        if (ref[k * W] & 1ull) return fail(RC_E_ARG, "a reference split holds position 0 (pass the other side)");
-        if ((n & 63) && ref[k * W + W - 1] >> (n & 63))
-            return fail(RC_E_ARG, "a reference split has bits at or above the sample count");
-    }
-    return RC_OK;
-}
-
-// Trees of the n_rep matrices at dD (device, n x n each) and the support of
-// the reference splits; the arguments have passed nj_check. Events ev[14],
-// ev[15]. *invalid: the number of matrices with a non-finite entry.
-static int nj_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t *joins, double *lengths,
-                     uint64_t *splits, uint8_t *valid, const uint64_t *ref, int32_t n_ref, uint32_t *support,
-                     uint32_t *n_valid, uint32_t *invalid)
-{
-    const int W = (n + 63) / 64;
-    const size_t R = (size_t)n_rep, nj = R * (size_t)(n - 2) * 3, ns = R * (size_t)(n - 3) * W;
-    CHK(e->d_nj_joins.ensure(nj));
-    CHK(e->d_nj_len.ensure(nj));
-    CHK(e->d_nj_splits.ensure(ns));
-    CHK(e->d_nj_valid.ensure(R));
-    CHK(e->d_nj_ref.ensure((size_t)n_ref * W));
-    CHK(e->d_nj_sup.ensure((size_t)n_ref + 1));
-    int lds_max = 0;
-    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
-    const bool lds = n <= e->knobs.nj_lds && nj_lds_bytes(true, n, W) <= (size_t)lds_max;
-    const size_t per = (size_t)n * n * 8 + (size_t)n * W * 8;
-    const size_t chunk = lds ? R : std::max<size_t>(1, std::min<size_t>(R, NJ_WS_BYTES / per));
-    if (!lds) {
-        CHK(e->d_nj_wsm.ensure(chunk * n * n));
-        CHK(e->d_nj_wsmask.ensure(chunk * n * W));
-    }
-    if (n_ref) HIPCHK(hipMemcpyAsync(e->d_nj_ref.p, ref, (size_t)n_ref * W * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemsetAsync(e->d_nj_sup.p, 0, ((size_t)n_ref + 1) * 4, e->st));
-    HIPCHK(hipEventRecord(e->ev[14], e->st));
-    for (size_t r0 = 0; r0 < R; r0 += chunk) {
-        const size_t rc = std::min(chunk, R - r0);
-        const hipError_t err = launch_nj(lds, dD + r0 * n * n, (int)rc, n, W, e->d_nj_wsm.p, e->d_nj_wsmask.p,
-                                         e->d_nj_joins.p + r0 * (n - 2) * 3, e->d_nj_len.p + r0 * (n - 2) * 3,
-                                         e->d_nj_splits.p + r0 * (n - 3) * W, e->d_nj_valid.p + r0, e->st);
-        if (err != hipSuccess)
-            return fail(RC_E_HIP, std::string("nj_kernel (") + std::to_string(nj_lds_bytes(lds, n, W)) +
-                                      " bytes of LDS): " + hipGetErrorString(err));
-    }
-    launch_nj_support(e->d_nj_ref.p, n_ref, e->d_nj_splits.p, e->d_nj_valid.p, n_rep, n - 3, W, e->d_nj_sup.p,
-                      e->d_nj_sup.p + n_ref, e->st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[15], e->st));
-    uint32_t nv = 0;
-    if (joins) HIPCHK(hipMemcpyAsync(joins, e->d_nj_joins.p, nj * 4, hipMemcpyDeviceToHost, e->st));
-    if (lengths) HIPCHK(hipMemcpyAsync(lengths, e->d_nj_len.p, nj * 8, hipMemcpyDeviceToHost, e->st));
-    if (splits && ns) HIPCHK(hipMemcpyAsync(splits, e->d_nj_splits.p, ns * 8, hipMemcpyDeviceToHost, e->st));
-    if (valid) HIPCHK(hipMemcpyAsync(valid, e->d_nj_valid.p, R, hipMemcpyDeviceToHost, e->st));
-    if (support && n_ref)
-        HIPCHK(hipMemcpyAsync(support, e->d_nj_sup.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(&nv, e->d_nj_sup.p + n_ref, 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.nj_ms = ev_ms(e, 14, 15);
-    if (n_valid) *n_valid = nv;
-    *invalid = (uint32_t)n_rep - nv;
-    return RC_OK;
-}
-
-extern "C" {
-
-int rc_nj(rc_engine *e, const double *D, int32_t n_rep, int32_t n, int32_t *joins, double *lengths, uint64_t *splits,
-          uint8_t *valid, const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid)
-{
-    if (!e) return fail(RC_E_ARG, "null argument");
-    CHK(nj_check(n_rep, n, ref_splits, n_ref, support));
-    if (!D) return fail(RC_E_ARG, "null argument");
-    CHK(set_device(e));
-    const size_t nd = (size_t)n_rep * n * n;
-    CHK(e->d_nj_in.ensure(nd));
-    HIPCHK(hipMemcpyAsync(e->d_nj_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
-    uint32_t invalid = 0;
-    CHK(nj_device(e, e->d_nj_in.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
-                  &invalid));
-    if (invalid) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no tree for it");
-    return RC_OK;
-}
-
-int rc_resample_trees(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
-                      int32_t n, int32_t *joins, double *lengths, uint64_t *splits, uint8_t *valid,
-                      const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid)
-{
-    if (!e) return fail(RC_E_ARG, "null argument");
-    CHK(nj_check(n_rep, n, ref_splits, n_ref, support));
-    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
-    uint32_t invalid = 0;
-    CHK(nj_device(e, e->d_dist.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
-                  &invalid));
-    e->tm.resample_ms = ev_ms(e, 12, 13);
-    if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
-    return RC_OK;
-}
-
-}  // extern "C"
-
-extern "C" {
 
 int rc_dust_mask(rc_engine *e, int32_t s, uint8_t *buf, uint64_t cap, uint64_t *n)
 {
@@ -3742,302 +2618,6 @@ int rc_shard_pairs(rc_engine *e, int64_t *first, int64_t *last)
     CHK(upload(e));
     *first = (int64_t)e->pair0;
     *last = (int64_t)e->pair1;
-    return RC_OK;
-}
-
-// graph.pkl from the engine's graph edges: build_graph over every pair's
-// table in combinations order (find_all_pairs.py:224-228 as the one-process
-// order; build_graph.py:40-68) needs, per pair, its distinct (s-gene, q-gene)
-// edges in the order of their first table rows -- the order of the edge
-// records of that pair. The records (all pairs: a single-shard run's own, a
-// sharded run's after rc_import_edges) are stably sorted on the device by
-// their pair's combinations rank and copied to the host; tbeg[k] is the first
-// record of the k-th non-empty pair.
-// graph.pkl's tables from the edge records: sorted on the device into every
-// pair's table in combinations order (stable: record order inside a pair),
-// then handed to the writer as node-slot pairs -- a record's genes are global
-// gene indices, sample-major, so sample s's nodes are the slots
-// [gene_base[s], gene_base[s + 1]) -- with the tables' row ranges. One
-// record per edge (the RBH kernel aggregates an edge's rows into it), so the
-// writer skips its edge deduplication.
-static int edge_slots(rc_engine *e, GraphSlots &G)
-{
-    if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    CHK(set_device(e));
-    const uint64_t n = e->n_edges;
-    const int N = (int)e->samples.size();
-    if (n > 0xFFFFFFFFull) return fail(RC_E_LIMIT, "more than 2^32 graph edges");
-    const size_t ncomb = e->pair_a.size();
-    std::vector<uint32_t> comb(ncomb);
-    for (size_t p = 0; p < ncomb; p++) {
-        const uint64_t a = (uint64_t)e->pair_a[p], b = (uint64_t)e->pair_b[p];
-        comb[p] = (uint32_t)(a * (2 * (uint64_t)N - a - 1) / 2 + (b - a - 1));
-    }
-    G = GraphSlots();
-    G.ns = N;
-    G.base.assign((size_t)N + 1, 0);
-    for (int32_t s : e->gene_sample) G.base[(size_t)s + 1]++;
-    for (int s = 0; s < N; s++) G.base[s + 1] += G.base[s];
-    G.slot_gene = e->gene_id.data();
-    G.unique = true;
-    G.rows = n;
-    std::vector<uint64_t> first(ncomb, ~0ull);
-    if (n) {
-        DBuf<uint32_t> dcomb, k0, k1, v0, v1;
-        DBuf<uint64_t> dfirst;
-        CHK(dcomb.ensure(ncomb));
-        CHK(dfirst.ensure(std::max<size_t>(ncomb, 1)));
-        CHK(k0.ensure(n));
-        CHK(k1.ensure(n));
-        CHK(v0.ensure(n));
-        CHK(v1.ensure(n));
-        HIPCHK(hipMemcpyAsync(dcomb.p, comb.data(), ncomb * 4, hipMemcpyHostToDevice, e->st));
-        HIPCHK(hipMemsetAsync(dfirst.p, 0xFF, ncomb * 8, e->st));
-        launch_edge_key(e->d_edges.p, n, dcomb.p, k0.p, v0.p, e->st);
-        HIPCHK(hipGetLastError());
-        size_t tmp = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, k0.p, k1.p, v0.p, v1.p, (size_t)n, 0u, 32u, e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::radix_sort_pairs(e->d_tmp.p, tmp, k0.p, k1.p, v0.p, v1.p, (size_t)n, 0u, 32u, e->st));
-        uint32_t last = 0;
-        HIPCHK(hipMemcpyAsync(&last, k1.p + n - 1, 4, hipMemcpyDeviceToHost, e->st));
-        // the (a, b) arrays reuse the sort's input buffers
-        launch_edge_uv(e->d_edges.p, v1.p, k1.p, n, k0.p, v0.p, dfirst.p, e->st);
-        HIPCHK(hipGetLastError());
-        G.U = Raw<uint32_t>(n);
-        G.V = Raw<uint32_t>(n);
-        HIPCHK(hipMemcpyAsync(G.U.data(), k0.p, n * 4, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(G.V.data(), v0.p, n * 4, hipMemcpyDeviceToHost, e->st));
-        if (ncomb) HIPCHK(hipMemcpyAsync(first.data(), dfirst.p, ncomb * 8, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
-        if (last == ~0u)
-            return fail(RC_E_STATE, "an imported graph with isolated nodes or rows outside it: no graph.pkl from edges");
-    }
-    // the tables: combinations with records, in order (a table ends where the
-    // next one starts)
-    uint64_t end = n;
-    std::vector<GraphSlots::Tab> rev;
-    for (size_t c = ncomb; c-- > 0;) {
-        if (first[c] == ~0ull) continue;
-        const uint64_t o = first[c];
-        rev.push_back(GraphSlots::Tab{e->gene_sample[G.U[o]], e->gene_sample[G.V[o]], o, end - o});
-        end = o;
-    }
-    G.tabs.assign(rev.rbegin(), rev.rend());
-    return RC_OK;
-}
-
-static int write_graph_slots(const rc_engine *e, GraphSlots &G, const char *path)
-{
-    std::vector<const char *> names;
-    for (const SampleRec &s : e->samples) names.push_back(s.label.c_str());
-    return graph_pickle_write_slots(G, path, (int32_t)names.size(), names.data());
-}
-
-extern "C" int rc_write_graph(rc_engine *e, const char *path, int32_t threads)
-{
-    if (!e || !path) return fail(RC_E_ARG, "null argument");
-    const char *otv = getenv("RC_OUT_TIMING");
-    const bool otime = otv && atoi(otv);
-    const auto t0 = std::chrono::steady_clock::now();
-    (void)threads;   // (the writer sizes its own pool)
-    GraphSlots G;
-    CHK(edge_slots(e, G));
-    if (otime)
-        fprintf(stderr, "rc_write_graph: edge records sorted and fetched %.3f s\n",
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    return write_graph_slots(e, G, path);
-}
-
-// The outputs a run writes next to matrix.h5: the od2 gene matches tables of
-// the given pairs (paths[i] for pair (s1[i], s2[i]), table_paths may be NULL)
-// and graph.pkl (graph_path, may be NULL; build_graph's graph over the pairs
-// in the given order -- every pair of a single-shard engine, in combinations
-// order). Each pair's rows leave the device once; the calling thread fetches
-// them in order, `threads` workers convert and write the tables (od2_tables.
-// cpp), one more thread builds and writes the pickle (graph_pickle.cpp) --
-// all outside the Python interpreter.
-int rc_write_outputs(rc_engine *e, int32_t n_pairs, const int32_t *s1, const int32_t *s2,
-                     const char *const *table_paths, const char *graph_path, int32_t threads)
-{
-    if (!e || n_pairs < 0 || (n_pairs && (!s1 || !s2))) return fail(RC_E_ARG, "null argument");
-    if (!table_paths && !graph_path) return RC_OK;
-    if (graph_path && e->o.shard_count != 1)
-        return fail(RC_E_STATE, "a sharded engine holds only its own pairs' rows: graph.pkl comes from the edges");
-    const int nt = std::max(1, std::min(64, (int)threads));
-    // RC_OUT_TIMING=1: where the time goes (stderr)
-    const char *otv = getenv("RC_OUT_TIMING");
-    const bool otime = otv && atoi(otv);
-    std::atomic<long long> t_fetch{0}, t_conv{0}, t_write{0}, t_gadd{0}, t_gwrite{0};
-    auto now_ns = []() {
-        return (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                   std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const long long t_start = now_ns();
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::pair<int, std::shared_ptr<PairRaw>>> tq, gq;
-    bool closed = false;
-    int in_flight = 0, err = RC_OK;
-    std::string err_msg;
-    auto set_err = [&](int code) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (err == RC_OK) {
-                err = code;
-                err_msg = rc_last_error();
-            }
-        }
-        cv.notify_all();   // the fetch loop may be waiting for room
-    };
-    // graph.pkl over every pair in combinations order comes from the edge
-    // records (sorted on the device first), written on its own thread beside
-    // the tables; other pair lists (and imported graphs) take the rows
-    GraphSlots gslots;
-    bool edge_graph = false;
-    if (graph_path) {
-        const int N = (int)e->samples.size();
-        bool all = (int64_t)n_pairs == (int64_t)N * (N - 1) / 2;
-        for (int a = 0, k = 0; all && a < N; a++)
-            for (int b = a + 1; all && b < N; b++, k++) all = s1[k] == a && s2[k] == b;
-        edge_graph = all && edge_slots(e, gslots) == RC_OK;
-    }
-    auto worker = [&]() {
-        std::vector<rc_row> buf;
-        for (;;) {
-            std::pair<int, std::shared_ptr<PairRaw>> job;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !tq.empty() || closed; });
-                if (tq.empty()) return;
-                job = std::move(tq.front());
-                tq.pop_front();
-            }
-            const PairRaw &raw = *job.second;
-            const int32_t js1 = raw.s1, js2 = raw.s2;
-            const long long c0 = now_ns();
-            buf.resize(raw.n);
-            convert_rows(e, raw, buf.data());
-            job.second.reset();   // (its slab goes back once the grapher is done too)
-            const long long c1 = now_ns();
-            const int rc = od2_write_table(buf.data(), buf.size(), e->samples[js1].label, e->samples[js2].label,
-                                           table_paths[job.first]);
-            t_conv += c1 - c0;
-            t_write += now_ns() - c1;
-            if (rc != RC_OK) set_err(rc);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                in_flight--;
-            }
-            cv.notify_all();
-        }
-    };
-    auto grapher = [&]() {
-        rc_gpickle *g = nullptr;
-        bool ok = true;
-        if (rc_graph_pickle_begin(&g) != RC_OK) {
-            // keep draining the queue (in_flight must still go down)
-            set_err(RC_E_NOMEM);
-            g = nullptr;
-            ok = false;
-        }
-        for (;;) {
-            std::pair<int, std::shared_ptr<PairRaw>> job;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !gq.empty() || closed; });
-                if (gq.empty()) break;
-                job = std::move(gq.front());
-                gq.pop_front();
-            }
-            const PairRaw &raw = *job.second;
-            const long long a0 = now_ns();
-            const size_t n = raw.n;
-            // the table's gene arrays, written in place (node numbering and
-            // edges happen in parallel when the pickle is written)
-            int64_t *sg = nullptr, *qg = nullptr;
-            if (ok && graph_pickle_table(g, raw.s1, raw.s2, n, &sg, &qg) != RC_OK) {
-                set_err(RC_E_LIMIT);
-                ok = false;
-            }
-            if (ok)
-                for (size_t i = 0; i < n; i++) {
-                    const DHsp &d = raw.hs[i];
-                    const bool rev = raw.rows[i].reverse != 0;
-                    qg[i] = e->tx_gene_id[rev ? d.s_tx : d.q_tx];   // qgene: the transcript of s2
-                    sg[i] = e->tx_gene_id[rev ? d.q_tx : d.s_tx];
-                }
-            t_gadd += now_ns() - a0;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                in_flight--;
-            }
-            cv.notify_all();
-        }
-        if (ok) {
-            const long long w0 = now_ns();
-            std::vector<const char *> names;
-            for (const SampleRec &s : e->samples) names.push_back(s.label.c_str());
-            if (rc_graph_pickle_write(g, graph_path, (int32_t)names.size(), names.data()) != RC_OK) set_err(RC_E_IO);
-            t_gwrite += now_ns() - w0;
-        }
-        rc_graph_pickle_free(g);
-    };
-    // every pair's row range first: the pinned slabs are sized to the largest
-    std::vector<uint64_t> ranges(2 * (size_t)n_pairs);
-    uint64_t max_rows = 0;
-    for (int i = 0; i < n_pairs && (table_paths || !edge_graph); i++) {
-        CHK(pair_row_range(e, s1[i], s2[i], ranges[2 * i], ranges[2 * i + 1]));
-        max_rows = std::max<uint64_t>(max_rows, ranges[2 * i + 1] - ranges[2 * i]);
-    }
-    SlabPool slabs;
-    slabs.bytes = std::max<uint64_t>(max_rows, 1) * (sizeof(DRow) + sizeof(DHsp));
-    slabs.cap = (size_t)(2 * nt + 8);
-    auto edge_grapher = [&]() {
-        const long long w0 = now_ns();
-        const int rc = write_graph_slots(e, gslots, graph_path);
-        if (rc != RC_OK) set_err(rc);
-        t_gwrite += now_ns() - w0;
-    };
-    std::vector<std::thread> pool;
-    if (table_paths)
-        for (int i = 0; i < nt; i++) pool.emplace_back(worker);
-    if (graph_path) pool.emplace_back(edge_graph ? std::function<void()>(edge_grapher) : std::function<void()>(grapher));
-    const bool row_graph = graph_path && !edge_graph;
-    const int per_job = (table_paths ? 1 : 0) + (row_graph ? 1 : 0);
-    const int max_flight = 4 * nt + 4;
-    int rc = RC_OK;
-    for (int i = 0; i < n_pairs && rc == RC_OK && per_job; i++) {
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return in_flight < max_flight * per_job || err != RC_OK; });
-            if (err != RC_OK) break;
-        }
-        auto raw = std::make_shared<PairRaw>();
-        const long long f0 = now_ns();
-        rc = fetch_pair(e, s1[i], s2[i], *raw, &slabs, &ranges[2 * (size_t)i]);
-        t_fetch += now_ns() - f0;
-        if (rc != RC_OK) break;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (table_paths) tq.push_back({i, raw});
-            if (row_graph) gq.push_back({i, raw});
-            in_flight += per_job;
-        }
-        cv.notify_all();
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        closed = true;
-    }
-    cv.notify_all();
-    for (std::thread &t : pool) t.join();
-    if (otime)
-        fprintf(stderr, "rc_write_outputs: %.3f s wall; fetch %.3f s, convert %.3f, table write %.3f (thread-s, %d threads), "
-                        "graph add %.3f, graph write %.3f\n", (now_ns() - t_start) * 1e-9, t_fetch * 1e-9, t_conv * 1e-9,
-                t_write * 1e-9, nt, t_gadd * 1e-9, t_gwrite * 1e-9);
-    if (rc != RC_OK) return rc;
-    if (err != RC_OK) return fail(err, err_msg);
     return RC_OK;
 }
 

@@ -25,8 +25,7 @@
 #include <vector>
 
 #include "../../include/rcgpu.h"
-
-int rcg_fail(int code, const std::string &msg);   // engine.hip
+#include "fail.h"
 
 struct rc_fasta {
     const char *data = nullptr;

@@ -28,6 +28,7 @@
 //    offset (page-cache writes from every thread; pwrite on one file
 //    serialises on the inode lock).
 #include "../../include/rcgpu.h"
+#include "fail.h"
 #include "graph_pickle.h"
 
 #include <cstdint>
@@ -46,8 +47,6 @@
 #include <memory>
 #include <string>
 #include <vector>
-
-int rcg_fail(int code, const std::string &msg);
 
 static constexpr size_t RAW_MAP_MIN = 32ull << 20;
 
@@ -413,7 +412,7 @@ void tables_to_slots(rc_gpickle *g, GraphSlots &G)
 
 }  // namespace
 
-// the whole write from slot form (engine.hip hands its device-sorted edge
+// the whole write from slot form (results.hip hands its device-sorted edge
 // records in this form; rc_graph_pickle_write its tables)
 int graph_pickle_write_slots(GraphSlots &G, const char *path, int32_t n_names, const char *const *names)
 {

@@ -13,6 +13,7 @@
 // The exact semantics are those of oracle/align_oracle.c (alignment) and
 // oracle/post_oracle.py (post-alignment, pinned to the reference).
 #include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <climits>

@@ -16,6 +16,7 @@
 // and the leaf masks live in LDS; above that, the same code runs with both in
 // a per-replicate global workspace (r, node ids and the reduction stay in LDS).
 #include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 

@@ -14,8 +14,9 @@
 // (superblock v0, v1 object headers, symbol-table groups, contiguous data).
 // Writing natively takes the pandas frame, the per-column Python work and the
 // GIL out of the tables leg of the wall clock; a pool of threads writes the
-// files of many pairs at once (rc_write_tables, engine.hip).
+// files of many pairs at once (rc_write_tables, results.hip).
 #include "../../include/rcgpu.h"
+#include "fail.h"
 
 #include <cmath>
 #include <cstdint>
@@ -28,8 +29,6 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
-
-int rcg_fail(int code, const std::string &msg);
 
 namespace od2 {
 

@@ -39,6 +39,7 @@
 // each with the 8-bit passes; more of them than the list holds and the whole
 // index is sorted by the 8-bit passes.
 #include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <functional>

@@ -1,15 +1,9 @@
 // Microbenchmark of the DUST kernel on random packed sequence (build with
 // -DDUST_VARIANT=... to time variants). Not part of the product.
-#include "../../rna_clique_amd/csrc/device.h"
+#include "../../rna_clique_amd/csrc/launch.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-namespace rcg {
-void launch_dust(bool, uint64_t, uint64_t, const uint64_t *, const uint64_t *, const uint64_t *, const TxInfo *, uint32_t, int,
-                 int, int, uint32_t *, uint64_t *, uint32_t, uint64_t *, hipStream_t);
-uint32_t dust_scratch_words(uint32_t);
-uint64_t dust_event_words(uint32_t);
-}
 using namespace rcg;
 int main(int argc, char **argv)
 {

@@ -10,7 +10,7 @@
 // epoch, kept across calls the way the engine's sort_index keeps them: the
 // status table is zeroed only when it grows, the epoch starts at 0 and is
 // advanced by the sort alone.
-#include "device.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <functional>
@@ -18,22 +18,6 @@
 #include <vector>
 
 namespace rcg {
-void launch_pack(const uint8_t *, uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_kmer_count(const TxInfo *, uint32_t, const uint64_t *, uint64_t *, hipStream_t);
-void launch_kmer_fill(bool, const TxInfo *, uint32_t, const uint64_t *, const uint64_t *, const uint64_t *,
-                      uint64_t *, hipStream_t);
-void launch_bucket_fill(const uint64_t *, uint64_t, int, uint32_t *, hipStream_t);
-int os_index_gbits(uint64_t n, int bits, uint32_t cap);
-uint64_t os_index_status_words(uint64_t n);
-uint64_t os_index_scratch_words(uint64_t n);
-uint64_t os_index_offset_words(int G);
-uint64_t os_index_list_words();
-void os_index_fill_hist(const TxInfo *tx, uint32_t n_tx, const uint64_t *F, const uint64_t *koff, uint64_t *ent,
-                        uint64_t n, int G, uint32_t *scratch, hipStream_t st);
-int os_index_sort(uint64_t *keys, uint64_t *alt, uint64_t n, int G, int bits, uint32_t cap, uint32_t *scratch,
-                  uint64_t *status, uint32_t &epoch, uint32_t *offsets, uint32_t *list, uint32_t *bucket,
-                  hipStream_t st, bool counted, const std::function<bool()> &wait, uint32_t *fb_ranges,
-                  uint64_t *fb_keys, bool *whole);
 int isp_tile_keys();
 int isp_local_cap();
 int isp_list_len();
@@ -44,7 +28,7 @@ using rcg::TxInfo;
 
 namespace {
 
-constexpr size_t FRONT_PAD = 2;   // engine.hip: zero words in front of every packed array
+constexpr size_t FRONT_PAD = 2;   // engine.h: zero words in front of every packed array
 constexpr size_t BACK_PAD = 4;    // and behind
 constexpr int ISP_E_ARG = -1, ISP_E_HIP = -2, ISP_E_CAP = -3;
 

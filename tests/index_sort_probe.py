@@ -48,7 +48,7 @@ def _stale():
         return True
     t = os.path.getmtime(LIB)
     csrc = _product().CSRC
-    deps = [SRC] + WRAPPERS + [os.path.join(csrc, s) for s in PRODUCT_SOURCES + ["device.h"]]
+    deps = [SRC] + WRAPPERS + [os.path.join(csrc, s) for s in PRODUCT_SOURCES + ["device.h", "launch.h"]]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

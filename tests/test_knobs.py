@@ -32,7 +32,7 @@ def _knobs_read():
 
 
 def test_knobs_read_are_the_knobs_documented():
-    documented = set(re.findall(r"//\s*(RC_[A-Z0-9_]+)\b", _body(_read(os.path.join(CSRC, "engine.hip")),
+    documented = set(re.findall(r"//\s*(RC_[A-Z0-9_]+)\b", _body(_read(os.path.join(CSRC, "engine.h")),
                                                                   "struct Knobs")))
     assert _knobs_read() and _knobs_read() == documented
 
