@@ -47,7 +47,8 @@ extern "C" {
  *                                 b bits (4095 at 16 Mbp)
  *   bases per alignment tile      2^32 (a shard is cut into tiles below that)
  *   seeds per (query gene, subject sample) pass 2^22
- *   samples in a neighbour-joining tree 1024 (rc_nj, rc_resample_trees) */
+ *   samples in a neighbour-joining tree 1024 (rc_nj, rc_resample_trees)
+ *   samples in a principal coordinates analysis 128 (rc_pcoa, rc_resample_pcoa) */
 #define RC_E_IO (-8)         /* file could not be written */
 
 typedef struct rc_engine rc_engine;
@@ -161,6 +162,8 @@ typedef struct rc_timing {
     double resample_ms;       /* device time of the last rc_resample's product kernel (zeroing its outputs
                                  included; the weights' upload and the distances are outside it) */
     double nj_ms;             /* device time of the last rc_nj / rc_resample_trees' tree and support kernels
+                                 (uploads and the copies back are outside it) */
+    double pcoa_ms;           /* device time of the last rc_pcoa / rc_resample_pcoa's eigensolver kernel
                                  (uploads and the copies back are outside it) */
 } rc_timing;
 
@@ -357,6 +360,50 @@ int rc_nj(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, int32_t *jo
 int rc_resample_trees(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
                       int32_t n, int32_t *joins, double *lengths, uint64_t *splits, uint8_t *valid,
                       const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid);
+
+/* ---- principal coordinates (PCoA, classical scaling) -----------------------
+ * The eigenvalues and eigenvectors of the Gower-centred matrix of every
+ * replicate, in float64 with a fixed operation order: of
+ * matrix D[n][n] only i < j is read. E = -0.5 * (d * d), mirrored, with a zero
+ * diagonal; rowmean[i] = (ascending sum of row i) / n, grand = (ascending sum
+ * of rowmean) / n; B[i][j] = ((E[i][j] - rowmean[i]) - rowmean[j]) + grand for
+ * i <= j, mirrored; sigma = ||B||_F. One-sided (Hestenes) Jacobi then makes
+ * the columns of A = B + sigma I orthogonal: sweeps in round-robin order (m = n
+ * rounded up to even; m - 1 steps of m / 2 disjoint pairs; step s pairs
+ * player m - 1 with s and (s + g) mod (m - 1) with (s - g) mod (m - 1), g = 1
+ * .. m / 2 - 1; a pair with the dummy player n of an odd n is skipped). For a
+ * pair p < q with alpha = a_p.a_p, beta = a_q.a_q, gamma = a_p.a_q: no
+ * rotation when alpha == 0, beta == 0 or |gamma| <= 2^-52 sqrt(alpha)
+ * sqrt(beta); else zeta = (beta - alpha) / (2 gamma), t = sgn(zeta) / (|zeta|
+ * + sqrt(1 + zeta^2)) with sgn(0) = +1, c = 1 / sqrt(1 + t^2), s = c t, and
+ * (a_p, a_q) <- (c a_p - s a_q, s a_p + c a_q). The sweeps end after the first
+ * one without a rotation, or after max_sweeps (0 = the default, 30). Column c
+ * is then (lambda_c + sigma) v_c: lambda_c = ||a_c|| - sigma, v_c = a_c /
+ * ||a_c|| (zero when the norm is 0: only B = 0 gives that, as trace(B) >= 0).
+ * The shift makes A positive semidefinite (sigma >= |lambda|): the norms are
+ * its eigenvalues, so eigenvalues of B of equal magnitude and opposite sign
+ * stay apart and no sign has to be recovered; every eigenvalue is accurate to
+ * O(n eps ||B||_F), not relative to itself.
+ *   values[r]   n eigenvalues, descending, ties by the lower column
+ *   vectors[r]  n x k, sample-major: the unit eigenvectors of the first k
+ *               values, each with its entry of largest magnitude positive (the
+ *               lowest sample among equal magnitudes)
+ *   sweeps[r]   sweeps run, the last, rotation-free one included
+ *   valid[r]    0 for a matrix with a non-finite entry above its diagonal or a
+ *               non-finite sigma: its values and vectors are NaN, its sweeps 0
+ * Any output may be NULL. RC_E_ARG: n < 2, n_rep < 1, k outside 1..n,
+ * max_sweeps < 0, NULL D. RC_E_LIMIT: n > 128 (checked first; the matrix
+ * lives in LDS, one workgroup per replicate). After filling the outputs:
+ * RC_E_NO_IDEAL when some matrix is invalid, else RC_E_LIMIT when some matrix
+ * still rotated in sweep max_sweeps (its outputs hold that state).
+ * rc_pcoa: n_rep caller matrices (host, n_rep x n x n), on an engine in any
+ * state. rc_resample_pcoa: rc_resample's replicate matrices for order[n],
+ * which never leave the device. */
+int rc_pcoa(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, int32_t k, int32_t max_sweeps,
+            double *values, double *vectors, int32_t *sweeps, uint8_t *valid);
+int rc_resample_pcoa(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                     int32_t n, int32_t k, int32_t max_sweeps, double *values, double *vectors, int32_t *sweeps,
+                     uint8_t *valid);
 int rc_timings(rc_engine *eng, rc_timing *t);
 /* The DUST mask of sample `s` after rc_run / rc_align: one byte per base of
  * its concatenated transcripts (1 = masked query base, spec 1b of the oracle);

@@ -1,5 +1,6 @@
 // Analyses of a finished engine's graph: per-component tables, bootstrap
-// resampling and neighbour-joining trees (kernels: components.hip, nj.hip).
+// resampling, neighbour-joining trees and principal coordinates (kernels:
+// components.hip, nj.hip, pcoa.hip).
 #include "engine.h"
 
 // ------------------------------------------------------------------------
@@ -323,6 +324,98 @@ int rc_resample_trees(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint
                   &invalid));
     e->tm.resample_ms = ev_ms(e, 12, 13);
     if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    return RC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// principal coordinates (pcoa.hip)
+// ------------------------------------------------------------------------
+
+static const int PCOA_MAX_SAMPLES = 128;
+static const int PCOA_SWEEPS = 30;   // max_sweeps == 0
+
+// the argument checks of rc_pcoa / rc_resample_pcoa (no device work)
+static int pcoa_check(int32_t n_rep, int32_t n, int32_t k, int32_t max_sweeps)
+{
+    if (n > PCOA_MAX_SAMPLES) return fail(RC_E_LIMIT, "more than 128 samples in a principal coordinates analysis");
+    if (n < 2) return fail(RC_E_ARG, "principal coordinates need at least 2 samples");
+    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
+    if (k < 1 || k > n) return fail(RC_E_ARG, "k must lie in 1..n");
+    if (max_sweeps < 0) return fail(RC_E_ARG, "max_sweeps must be >= 0");
+    return RC_OK;
+}
+
+// Eigenvalues and the first k eigenvectors of the n_rep matrices at dD
+// (device, n x n each); the arguments have passed pcoa_check. Events ev[16],
+// ev[17]. stat[0]: matrices with a non-finite entry or norm, stat[1]: matrices
+// that still rotated in their last allowed sweep.
+static int pcoa_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t k, int32_t max_sweeps,
+                       double *values, double *vectors, int32_t *sweeps, uint8_t *valid, unsigned int stat[2])
+{
+    const size_t R = (size_t)n_rep, nv = R * (size_t)n, nx = nv * (size_t)k;
+    if (!max_sweeps) max_sweeps = PCOA_SWEEPS;
+    int lds_max = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
+    if (pcoa_lds_bytes(n) + 4096 > (size_t)lds_max)
+        return fail(RC_E_LIMIT, "this device's LDS does not hold a matrix of " + std::to_string(n) + " samples");
+    CHK(e->d_pcoa_val.ensure(nv));
+    CHK(e->d_pcoa_vec.ensure(nx));
+    CHK(e->d_pcoa_sweeps.ensure(R));
+    CHK(e->d_pcoa_valid.ensure(R));
+    CHK(e->d_pcoa_stat.ensure(2));
+    HIPCHK(hipMemsetAsync(e->d_pcoa_stat.p, 0, 2 * sizeof(unsigned int), e->st));
+    HIPCHK(hipEventRecord(e->ev[16], e->st));
+    const hipError_t err = launch_pcoa(dD, n_rep, n, k, max_sweeps, e->d_pcoa_val.p, e->d_pcoa_vec.p,
+                                       e->d_pcoa_sweeps.p, e->d_pcoa_valid.p, e->d_pcoa_stat.p, e->st);
+    if (err != hipSuccess)
+        return fail(RC_E_HIP, std::string("pcoa_kernel (") + std::to_string(pcoa_lds_bytes(n)) +
+                                  " bytes of LDS): " + hipGetErrorString(err));
+    HIPCHK(hipEventRecord(e->ev[17], e->st));
+    if (values) HIPCHK(hipMemcpyAsync(values, e->d_pcoa_val.p, nv * 8, hipMemcpyDeviceToHost, e->st));
+    if (vectors) HIPCHK(hipMemcpyAsync(vectors, e->d_pcoa_vec.p, nx * 8, hipMemcpyDeviceToHost, e->st));
+    if (sweeps) HIPCHK(hipMemcpyAsync(sweeps, e->d_pcoa_sweeps.p, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (valid) HIPCHK(hipMemcpyAsync(valid, e->d_pcoa_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(stat, e->d_pcoa_stat.p, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.pcoa_ms = ev_ms(e, 16, 17);
+    return RC_OK;
+}
+
+static int pcoa_unconverged() { return fail(RC_E_LIMIT, "a matrix still rotated in its last allowed Jacobi sweep"); }
+
+extern "C" {
+
+int rc_pcoa(rc_engine *e, const double *D, int32_t n_rep, int32_t n, int32_t k, int32_t max_sweeps, double *values,
+            double *vectors, int32_t *sweeps, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    CHK(pcoa_check(n_rep, n, k, max_sweeps));
+    if (!D) return fail(RC_E_ARG, "null argument");
+    CHK(set_device(e));
+    const size_t nd = (size_t)n_rep * n * n;
+    CHK(e->d_pcoa_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->d_pcoa_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
+    unsigned int stat[2] = {};
+    CHK(pcoa_device(e, e->d_pcoa_in.p, n_rep, n, k, max_sweeps, values, vectors, sweeps, valid, stat));
+    if (stat[0]) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no ordination for it");
+    if (stat[1]) return pcoa_unconverged();
+    return RC_OK;
+}
+
+int rc_resample_pcoa(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                     int32_t n, int32_t k, int32_t max_sweeps, double *values, double *vectors, int32_t *sweeps,
+                     uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    CHK(pcoa_check(n_rep, n, k, max_sweeps));
+    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
+    unsigned int stat[2] = {};
+    CHK(pcoa_device(e, e->d_dist.p, n_rep, n, k, max_sweeps, values, vectors, sweeps, valid, stat));
+    e->tm.resample_ms = ev_ms(e, 12, 13);
+    if (stat[0]) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    if (stat[1]) return pcoa_unconverged();
     return RC_OK;
 }
 

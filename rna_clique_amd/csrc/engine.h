@@ -330,13 +330,19 @@ struct rc_engine {
     DBuf<uint64_t> d_nj_splits, d_nj_ref, d_nj_wsmask;
     DBuf<uint8_t> d_nj_valid;
     DBuf<uint32_t> d_nj_sup;
+    // principal coordinates (pcoa.hip): input matrices of rc_pcoa, the results
+    // and the status words (invalid, unconverged replicates)
+    DBuf<double> d_pcoa_in, d_pcoa_val, d_pcoa_vec;
+    DBuf<int32_t> d_pcoa_sweeps;
+    DBuf<uint8_t> d_pcoa_valid;
+    DBuf<unsigned int> d_pcoa_stat;
 
     // host results
     std::vector<unsigned long long> h_num, h_den, h_num_all, h_den_all, h_stats;
     std::vector<double> h_ss;   // search space of a query of length L against sample T: [T][L]
     std::vector<double> h_exp;  // exp(-lambda * S / 2) per raw score in half units S (stats::evalue's factor)
     rc_timing tm{};
-    hipEvent_t ev[16] = {};
+    hipEvent_t ev[18] = {};
     hipEvent_t evd[3] = {};   // DUST start / end on st2, its start condition on st
 
     ~rc_engine()

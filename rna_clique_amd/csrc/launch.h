@@ -1,5 +1,5 @@
 // The host entry points of the kernel files: every non-static host function
-// that kernels.hip, components.hip, nj.hip, sort.hip, align.hip and dust.hip
+// that kernels.hip, components.hip, nj.hip, pcoa.hip, sort.hip, align.hip and dust.hip
 // define, declared here and nowhere else. The defining files include this
 // header too, so a definition whose return type drifts from its declaration
 // does not compile.
@@ -53,6 +53,11 @@ size_t nj_lds_bytes(bool, int, int);
 hipError_t launch_nj(bool, const double *, int, int, int, double *, uint64_t *, int32_t *, double *, uint64_t *,
                      uint8_t *, hipStream_t);
 void launch_nj_support(const uint64_t *, int, const uint64_t *, const uint8_t *, int, int, int, uint32_t *, uint32_t *,
+                       hipStream_t);
+// pcoa.hip
+int pcoa_ld(int);
+size_t pcoa_lds_bytes(int);
+hipError_t launch_pcoa(const double *, int, int, int, int, double *, double *, int32_t *, uint8_t *, unsigned int *,
                        hipStream_t);
 // sort.hip
 uint64_t os_status_words(uint64_t n);

@@ -404,6 +404,68 @@ class Engine:
             nat.check(code)
         return [self.labels[i] for i in order], NJResult(n_valid=nv.value, **bufs)
 
+    # ------------------------------------------------- principal coordinates
+    @staticmethod
+    def _pcoa_buffers(r, m, k):
+        k = m if k is None else int(k)
+        # the library checks the arguments; the buffers only have to exist
+        kk = min(max(k, 0), max(m, 0))
+        bufs = {"values": np.zeros((r, m), dtype=np.float64), "vectors": np.zeros((r, m, kk), dtype=np.float64),
+                "sweeps": np.zeros(r, dtype=np.int32), "valid": np.zeros(r, dtype=np.uint8)}
+        return k, bufs, [a.ctypes.data_as(ctypes.c_void_p) for a in bufs.values()]
+
+    def pcoa(self, matrices, k=None, *, max_sweeps=0, allow_nan=False):
+        """Principal coordinates of distance matrices (R, N, N) or (N, N), of
+        which only the part above the diagonal is read (rc_pcoa; the engine
+        may be in any state; N <= 128, else pcoa.pcoa_eigh on the host).
+        Returns pcoa.PCoAEigen: values (R, N) descending, the first k (default
+        N) unit eigenvectors (R, N, k), sweeps and valid. Raises
+        NativeError(RC_E_NO_IDEAL) when a matrix has a non-finite entry, unless
+        allow_nan (that replicate is then NaN and flagged in `valid`), and
+        NativeError(RC_E_LIMIT) when one has not converged in max_sweeps
+        (0 = the default, 30) sweeps."""
+        from .pcoa import PCoAEigen
+        d = np.ascontiguousarray(matrices, dtype=np.float64)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1] != d.shape[2]:
+            raise ValueError("matrices must have shape (replicates, N, N)")
+        r, m = d.shape[0], d.shape[1]
+        k, bufs, ptrs = self._pcoa_buffers(r, m, k)
+        code = nat.lib().rc_pcoa(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, k, int(max_sweeps), *ptrs)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return PCoAEigen(**bufs)
+
+    def resample_pcoa(self, weights, order=None, k=None, *, max_sweeps=0, allow_nan=False):
+        """The principal coordinates of every replicate of resample(weights,
+        order): the matrices stay on the device (rc_resample_pcoa). Returns
+        (labels, pcoa.PCoAEigen); row i of a replicate's vectors stands for
+        labels[i]. Errors as pcoa(); RC_E_NO_IDEAL: a replicate has a pair
+        without rows."""
+        from .pcoa import PCoAEigen
+        w = np.asarray(weights)
+        if w.ndim != 2:
+            raise ValueError("weights must have shape (replicates, components)")
+        if w.dtype != np.uint16:
+            if w.dtype.kind not in "iu":
+                raise TypeError("weights must be integers")
+            if w.size and (w.min() < 0 or w.max() > 65535):
+                raise ValueError("weights must lie in 0..65535")
+        w = np.ascontiguousarray(w, dtype=np.uint16)
+        n = len(self.labels)
+        if order is None:
+            order = sorted(range(n), key=lambda i: self.labels[i])
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        m, r = len(order), w.shape[0]
+        k, bufs, ptrs = self._pcoa_buffers(r, m, k)
+        vp = ctypes.c_void_p
+        code = nat.lib().rc_resample_pcoa(self._h, w.ctypes.data_as(vp), r, w.shape[1], order.ctypes.data_as(vp), m,
+                                          k, int(max_sweeps), *ptrs)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return [self.labels[i] for i in order], PCoAEigen(**bufs)
+
     def dust_mask(self, s):
         """DUST mask of sample s (uint8 per base, 1 = masked query base)."""
         return self._sized(nat.lib().rc_dust_mask, np.uint8, int(s))

@@ -443,6 +443,72 @@ class SampleSimilarity:
         res = self._resample_trees(bootstrap_weights(self.engine.n_components(), n_rep, seed), tree.splits)
         return NJTree(tree.labels, tree.joins, tree.lengths, tree.splits, res.support / float(res.n_valid))
 
+    # ------------------------------------------- principal coordinates
+    def _pcoa_order(self, dimensions, clip=False):
+        """This object's sample order and the number of axes, checked; clip:
+        more axes than samples mean all of them."""
+        from .pcoa import MAX_GPU_SAMPLES
+        o = self._order()
+        if len(o) < 2:
+            raise ValueError("principal coordinates need at least 2 samples")
+        if len(o) > MAX_GPU_SAMPLES:
+            raise ValueError(f"more than {MAX_GPU_SAMPLES} samples: use rna_clique_amd.pcoa.pcoa_eigh on "
+                             "get_dissimilarity_matrix() or on the resampled matrices")
+        k = len(o) if dimensions is None else int(dimensions)
+        if clip:
+            k = min(k, len(o))
+        if not 1 <= k <= len(o):
+            raise ValueError("dimensions must lie in 1..number of samples")
+        return o, k
+
+    def _resample_pcoa(self, weights, dimensions):
+        """Engine.resample_pcoa in this object's sample order."""
+        o, k = self._pcoa_order(dimensions)
+        try:
+            return self.engine.resample_pcoa(weights, o, k)[1]
+        except nat.NativeError as e:
+            if e.code == nat.RC_E_NO_IDEAL:
+                raise NoIdealComponentsError() from e
+            raise
+
+    def pcoa(self, dimensions=None):
+        """The principal coordinates (pcoa.PCoAResult) of
+        get_dissimilarity_matrix() -- the replicate of all-ones weights, which
+        is that matrix bit for bit -- computed on the GPU: what viz/pcoa.py
+        gets from skbio.stats.ordination.pcoa. `dimensions`: the number of
+        axes in `samples` (default: all); eigvals always holds all of them."""
+        from .pcoa import PCoAResult
+        self._pcoa_order(dimensions)
+        c = self.engine.n_components()
+        if c == 0:
+            raise NoIdealComponentsError()
+        res = self._resample_pcoa(np.ones((1, c), dtype=np.uint16), dimensions)
+        return PCoAResult(self.samples, res.values[0], res.vectors[0])
+
+    def resampled_pcoa(self, weights, dimensions=3) -> np.ndarray:
+        """The principal coordinates of every row of `weights`: (R, M,
+        dimensions) -- at most M axes --, the ordinations of resampled_dissimilarity_matrices(weights)
+        built on the GPU without the matrices leaving it, each rotated and
+        reflected onto pcoa()'s first `dimensions` axes (pcoa.procrustes_align;
+        an ordination's axes are defined up to that). Negative eigenvalues'
+        axes are zero, as in pcoa()."""
+        from .pcoa import clamp, procrustes_align
+        dims = self._pcoa_order(dimensions, clip=True)[1]
+        ref = self.pcoa(dims)
+        res = self._resample_pcoa(weights, dims)
+        _, coords, _ = clamp(res.values, res.vectors)
+        return procrustes_align(coords, ref.coordinates)
+
+    def bootstrap_pcoa(self, n_rep, seed=0, dimensions=3):
+        """(pcoa(dimensions), the aligned coordinates (n_rep, M, dimensions) of
+        n_rep bootstrap replicates over the ideal components): the spread of a
+        sample's replicate positions is the analogue of split support for the
+        ordination."""
+        dims = self._pcoa_order(dimensions, clip=True)[1]
+        ref = self.pcoa(dims)
+        w = bootstrap_weights(self.engine.n_components(), n_rep, seed)
+        return ref, self.resampled_pcoa(w, dims)
+
 
 def _table_sums(df: pd.DataFrame):
     """(sum nident, sum length - sum gaps) of one gene matches table, as exact
