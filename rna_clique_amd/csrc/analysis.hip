@@ -15,25 +15,25 @@ enum { CS_MEMBERS = 0, CS_MAXCELL = 1, CS_BAD = 2, CS_N = 4 };   // slots of d_c
 static int build_components(rc_engine *e)
 {
     if (!e->finished) return fail(RC_E_STATE, "no results yet");
-    if (e->comp_valid) return RC_OK;
+    if (e->an.comp_valid) return RC_OK;
     CHK(set_device(e));
     const uint32_t ng = (uint32_t)e->gene_sample.size();
     const uint64_t P = e->pair_a.size();
     const uint64_t S = e->h_stats[4];
     uint64_t C = 0;
-    CHK(e->d_crank.ensure(ng));
-    CHK(e->d_cstat.ensure(CS_N));
-    HIPCHK(hipMemsetAsync(e->d_cstat.p, 0, CS_N * sizeof(unsigned long long), e->st));
+    CHK(e->an.d_crank.ensure(ng));
+    CHK(e->an.d_cstat.ensure(CS_N));
+    HIPCHK(hipMemsetAsync(e->an.d_cstat.p, 0, CS_N * sizeof(unsigned long long), e->st));
     if (ng) {
         size_t tmp = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->d_ideal.p, e->d_crank.p, 0u, (size_t)ng,
+        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->d_ideal.p, e->an.d_crank.p, 0u, (size_t)ng,
                                        rocprim::plus<uint32_t>(), e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::exclusive_scan(e->d_tmp.p, tmp, e->d_ideal.p, e->d_crank.p, 0u, (size_t)ng,
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->work.d_tmp.p, tmp, e->d_ideal.p, e->an.d_crank.p, 0u, (size_t)ng,
                                        rocprim::plus<uint32_t>(), e->st));
         uint32_t last_rank = 0;
         uint8_t last_ideal = 0;
-        HIPCHK(hipMemcpyAsync(&last_rank, e->d_crank.p + ng - 1, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&last_rank, e->an.d_crank.p + ng - 1, 4, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(&last_ideal, e->d_ideal.p + ng - 1, 1, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipStreamSynchronize(e->st));
         C = (uint64_t)last_rank + last_ideal;
@@ -42,47 +42,47 @@ static int build_components(rc_engine *e)
     if (C && !S) return fail(RC_E_STATE, "ideal components without a sample count");
     // members: sort (component id, gene) keys, the members come first
     const uint64_t nm = C * S;
-    CHK(e->d_cmember.ensure(nm));
+    CHK(e->an.d_cmember.ensure(nm));
     if (nm) {
         DBuf<uint64_t> k0, k1;
         CHK(k0.ensure(ng));
         CHK(k1.ensure(ng));
-        launch_comp_keys(e->d_parent.p, e->d_present.p, e->d_ideal.p, e->d_crank.p, ng, k0.p,
-                         e->d_cstat.p + CS_MEMBERS, e->st);
+        launch_comp_keys(e->d_parent.p, e->d_present.p, e->d_ideal.p, e->an.d_crank.p, ng, k0.p,
+                         e->an.d_cstat.p + CS_MEMBERS, e->st);
         HIPCHK(hipGetLastError());
         size_t tmp = 0;
         HIPCHK(rocprim::radix_sort_keys(nullptr, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::radix_sort_keys(e->d_tmp.p, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::radix_sort_keys(e->work.d_tmp.p, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
         unsigned long long members = 0;
-        HIPCHK(hipMemcpyAsync(&members, e->d_cstat.p + CS_MEMBERS, 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&members, e->an.d_cstat.p + CS_MEMBERS, 8, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipStreamSynchronize(e->st));
         if (members != nm) return fail(RC_E_STATE, "ideal components do not hold sample_count members each");
-        launch_comp_members(k1.p, nm, (uint32_t)S, e->d_cmember.p, e->d_cstat.p + CS_BAD, e->st);
+        launch_comp_members(k1.p, nm, (uint32_t)S, e->an.d_cmember.p, e->an.d_cstat.p + CS_BAD, e->st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(e->st));   // k0, k1 go out of scope
     }
     // sums, packed cells, largest cell
     const uint64_t cells = C * P;
-    CHK(e->d_cnum.ensure(cells));
-    CHK(e->d_cden.ensure(cells));
-    CHK(e->d_ccell.ensure(cells));
+    CHK(e->an.d_cnum.ensure(cells));
+    CHK(e->an.d_cden.ensure(cells));
+    CHK(e->an.d_ccell.ensure(cells));
     if (cells) {
-        HIPCHK(hipMemsetAsync(e->d_cnum.p, 0, cells * 8, e->st));
-        HIPCHK(hipMemsetAsync(e->d_cden.p, 0, cells * 8, e->st));
-        launch_comp_sums(e->d_edges.p, e->n_edges, e->d_parent.p, e->d_ideal.p, e->d_crank.p, P, e->d_cnum.p,
-                         e->d_cden.p, e->st);
-        launch_comp_pack(e->d_cnum.p, e->d_cden.p, cells, e->d_ccell.p, e->d_cstat.p + CS_MAXCELL, e->st);
+        HIPCHK(hipMemsetAsync(e->an.d_cnum.p, 0, cells * 8, e->st));
+        HIPCHK(hipMemsetAsync(e->an.d_cden.p, 0, cells * 8, e->st));
+        launch_comp_sums(e->d_edges.p, e->n_edges, e->d_parent.p, e->d_ideal.p, e->an.d_crank.p, P, e->an.d_cnum.p,
+                         e->an.d_cden.p, e->st);
+        launch_comp_pack(e->an.d_cnum.p, e->an.d_cden.p, cells, e->an.d_ccell.p, e->an.d_cstat.p + CS_MAXCELL, e->st);
         HIPCHK(hipGetLastError());
     }
     unsigned long long st[CS_N] = {};
-    HIPCHK(hipMemcpyAsync(st, e->d_cstat.p, sizeof st, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(st, e->an.d_cstat.p, sizeof st, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
     if (st[CS_BAD]) return fail(RC_E_STATE, "ideal components do not hold sample_count members each");
-    e->comp_n = C;
-    e->comp_S = (uint32_t)S;
-    e->comp_max_cell = st[CS_MAXCELL];
-    e->comp_valid = true;
+    e->an.comp_n = C;
+    e->an.comp_S = (uint32_t)S;
+    e->an.comp_max_cell = st[CS_MAXCELL];
+    e->an.comp_valid = true;
     return RC_OK;
 }
 
@@ -93,15 +93,15 @@ int rc_ideal_components(rc_engine *e, int32_t *sample, int32_t *gene, uint64_t c
 {
     if (!e || !n_comp || !sample_count) return fail(RC_E_ARG, "null argument");
     CHK(build_components(e));
-    *n_comp = e->comp_n;
-    *sample_count = (int32_t)e->comp_S;
+    *n_comp = e->an.comp_n;
+    *sample_count = (int32_t)e->an.comp_S;
     if (!sample && !gene) return RC_OK;
     if (!sample || !gene) return fail(RC_E_ARG, "null argument");
-    const uint64_t nm = e->comp_n * e->comp_S;
+    const uint64_t nm = e->an.comp_n * e->an.comp_S;
     if (cap_nodes < nm) return fail(RC_E_CAPACITY, "buffer too small");
     if (!nm) return RC_OK;
     std::vector<uint32_t> m(nm);
-    HIPCHK(hipMemcpy(m.data(), e->d_cmember.p, nm * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(m.data(), e->an.d_cmember.p, nm * 4, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < nm; i++) {
         sample[i] = e->gene_sample[m[i]];
         gene[i] = e->gene_id[m[i]];
@@ -114,15 +114,15 @@ int rc_component_sums(rc_engine *e, int64_t *num, int64_t *den, uint64_t cap_cel
 {
     if (!e || !n_comp || !n_pairs) return fail(RC_E_ARG, "null argument");
     CHK(build_components(e));
-    *n_comp = e->comp_n;
+    *n_comp = e->an.comp_n;
     *n_pairs = e->pair_a.size();
     if (!num && !den) return RC_OK;
     if (!num || !den) return fail(RC_E_ARG, "null argument");
-    const uint64_t cells = e->comp_n * e->pair_a.size();
+    const uint64_t cells = e->an.comp_n * e->pair_a.size();
     if (cap_cells < cells) return fail(RC_E_CAPACITY, "buffer too small");
     if (!cells) return RC_OK;
-    HIPCHK(hipMemcpy(num, e->d_cnum.p, cells * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(den, e->d_cden.p, cells * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(num, e->an.d_cnum.p, cells * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(den, e->an.d_cden.p, cells * 8, hipMemcpyDeviceToHost));
     return RC_OK;
 }
 
@@ -131,12 +131,12 @@ int rc_component_sums(rc_engine *e, int64_t *num, int64_t *den, uint64_t cap_cel
 // rc_resample up to the filled device buffers: the replicate sums in d_rnum /
 // d_rden and, with `dist`, the n_rep x n x n distances in d_dist with their
 // status word in d_status (queued on the stream, not waited for). Events
-// ev[12], ev[13].
+// EV_RESAMPLE0, EV_RESAMPLE1.
 static int resample_fill(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
                          int32_t n, bool dist, bool sums_paired)
 {
     CHK(build_components(e));
-    const uint64_t C = e->comp_n, P = e->pair_a.size();
+    const uint64_t C = e->an.comp_n, P = e->pair_a.size();
     const int N = (int)e->samples.size();
     if (n_comp != C) return fail(RC_E_ARG, "n_comp is not the number of ideal components");
     if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
@@ -151,7 +151,7 @@ static int resample_fill(rc_engine *e, const uint16_t *weights, int32_t n_rep, u
             seen[order[i]] = 1;
         }
     }
-    if (e->comp_max_cell >> 32) return fail(RC_E_LIMIT, "a component sum of 2^32 or more (stacked sums-only records)");
+    if (e->an.comp_max_cell >> 32) return fail(RC_E_LIMIT, "a component sum of 2^32 or more (stacked sums-only records)");
     const uint64_t R = (uint64_t)n_rep;
     uint16_t maxw = 0;
     for (uint64_t i = 0, nw = R * C; i < nw; i++) maxw = std::max(maxw, weights[i]);
@@ -162,26 +162,26 @@ static int resample_fill(rc_engine *e, const uint16_t *weights, int32_t n_rep, u
         return fail(RC_E_LIMIT, "weights this large could overflow the 64-bit replicate sums");
     CHK(set_device(e));
     const uint64_t cells = R * P;
-    CHK(e->d_rweight.ensure(R * C));
-    CHK(e->d_rnum.ensure(cells));
-    CHK(e->d_rden.ensure(cells));
-    if (R * C) HIPCHK(hipMemcpyAsync(e->d_rweight.p, weights, R * C * 2, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipEventRecord(e->ev[12], e->st));
+    CHK(e->an.d_rweight.ensure(R * C));
+    CHK(e->an.d_rnum.ensure(cells));
+    CHK(e->an.d_rden.ensure(cells));
+    if (R * C) HIPCHK(hipMemcpyAsync(e->an.d_rweight.p, weights, R * C * 2, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_RESAMPLE0], e->st));
     if (cells) {
-        HIPCHK(hipMemsetAsync(e->d_rnum.p, 0, cells * 8, e->st));
-        HIPCHK(hipMemsetAsync(e->d_rden.p, 0, cells * 8, e->st));
-        if (!launch_resample(e->d_ccell.p, e->d_rweight.p, C, P, (uint32_t)n_rep, e->d_rnum.p, e->d_rden.p, e->st))
+        HIPCHK(hipMemsetAsync(e->an.d_rnum.p, 0, cells * 8, e->st));
+        HIPCHK(hipMemsetAsync(e->an.d_rden.p, 0, cells * 8, e->st));
+        if (!launch_resample(e->an.d_ccell.p, e->an.d_rweight.p, C, P, (uint32_t)n_rep, e->an.d_rnum.p, e->an.d_rden.p, e->st))
             return fail(RC_E_LIMIT, "n_rep x pairs beyond the resample grid");
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(e->ev[13], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_RESAMPLE1], e->st));
     const uint64_t nd = dist ? R * (uint64_t)n * (uint64_t)n : 0;
     if (nd) {
         CHK(e->d_order.ensure(n));
         CHK(e->d_dist.ensure(nd));
         HIPCHK(hipMemcpyAsync(e->d_order.p, order, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
         HIPCHK(hipMemsetAsync(e->d_status.p, 0, sizeof(unsigned int), e->st));
-        launch_resample_distance(e->d_rnum.p, e->d_rden.p, e->d_pair_index.p, e->d_order.p, N, n, R, P, e->d_dist.p,
+        launch_resample_distance(e->an.d_rnum.p, e->an.d_rden.p, e->d_pair_index.p, e->d_order.p, N, n, R, P, e->d_dist.p,
                                  e->d_status.p, e->st);
         HIPCHK(hipGetLastError());
     }
@@ -203,11 +203,11 @@ int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, 4, hipMemcpyDeviceToHost, e->st));
     }
     if (num && cells) {
-        HIPCHK(hipMemcpyAsync(num, e->d_rnum.p, cells * 8, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipMemcpyAsync(den, e->d_rden.p, cells * 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(num, e->an.d_rnum.p, cells * 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(den, e->an.d_rden.p, cells * 8, hipMemcpyDeviceToHost, e->st));
     }
     HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.resample_ms = ev_ms(e, 12, 13);
+    e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
     if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;
 }
@@ -239,55 +239,55 @@ static int nj_check(int32_t n_rep, int32_t n, const uint64_t *ref, int32_t n_ref
 }
 
 // Trees of the n_rep matrices at dD (device, n x n each) and the support of
-// the reference splits; the arguments have passed nj_check. Events ev[14],
-// ev[15]. *invalid: the number of matrices with a non-finite entry.
+// the reference splits; the arguments have passed nj_check. Events EV_NJ0,
+// EV_NJ1. *invalid: the number of matrices with a non-finite entry.
 static int nj_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t *joins, double *lengths,
                      uint64_t *splits, uint8_t *valid, const uint64_t *ref, int32_t n_ref, uint32_t *support,
                      uint32_t *n_valid, uint32_t *invalid)
 {
     const int W = (n + 63) / 64;
     const size_t R = (size_t)n_rep, nj = R * (size_t)(n - 2) * 3, ns = R * (size_t)(n - 3) * W;
-    CHK(e->d_nj_joins.ensure(nj));
-    CHK(e->d_nj_len.ensure(nj));
-    CHK(e->d_nj_splits.ensure(ns));
-    CHK(e->d_nj_valid.ensure(R));
-    CHK(e->d_nj_ref.ensure((size_t)n_ref * W));
-    CHK(e->d_nj_sup.ensure((size_t)n_ref + 1));
+    CHK(e->an.d_nj_joins.ensure(nj));
+    CHK(e->an.d_nj_len.ensure(nj));
+    CHK(e->an.d_nj_splits.ensure(ns));
+    CHK(e->an.d_nj_valid.ensure(R));
+    CHK(e->an.d_nj_ref.ensure((size_t)n_ref * W));
+    CHK(e->an.d_nj_sup.ensure((size_t)n_ref + 1));
     int lds_max = 0;
     HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
     const bool lds = n <= e->knobs.nj_lds && nj_lds_bytes(true, n, W) <= (size_t)lds_max;
     const size_t per = (size_t)n * n * 8 + (size_t)n * W * 8;
     const size_t chunk = lds ? R : std::max<size_t>(1, std::min<size_t>(R, NJ_WS_BYTES / per));
     if (!lds) {
-        CHK(e->d_nj_wsm.ensure(chunk * n * n));
-        CHK(e->d_nj_wsmask.ensure(chunk * n * W));
+        CHK(e->an.d_nj_wsm.ensure(chunk * n * n));
+        CHK(e->an.d_nj_wsmask.ensure(chunk * n * W));
     }
-    if (n_ref) HIPCHK(hipMemcpyAsync(e->d_nj_ref.p, ref, (size_t)n_ref * W * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemsetAsync(e->d_nj_sup.p, 0, ((size_t)n_ref + 1) * 4, e->st));
-    HIPCHK(hipEventRecord(e->ev[14], e->st));
+    if (n_ref) HIPCHK(hipMemcpyAsync(e->an.d_nj_ref.p, ref, (size_t)n_ref * W * 8, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemsetAsync(e->an.d_nj_sup.p, 0, ((size_t)n_ref + 1) * 4, e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_NJ0], e->st));
     for (size_t r0 = 0; r0 < R; r0 += chunk) {
         const size_t rc = std::min(chunk, R - r0);
-        const hipError_t err = launch_nj(lds, dD + r0 * n * n, (int)rc, n, W, e->d_nj_wsm.p, e->d_nj_wsmask.p,
-                                         e->d_nj_joins.p + r0 * (n - 2) * 3, e->d_nj_len.p + r0 * (n - 2) * 3,
-                                         e->d_nj_splits.p + r0 * (n - 3) * W, e->d_nj_valid.p + r0, e->st);
+        const hipError_t err = launch_nj(lds, dD + r0 * n * n, (int)rc, n, W, e->an.d_nj_wsm.p, e->an.d_nj_wsmask.p,
+                                         e->an.d_nj_joins.p + r0 * (n - 2) * 3, e->an.d_nj_len.p + r0 * (n - 2) * 3,
+                                         e->an.d_nj_splits.p + r0 * (n - 3) * W, e->an.d_nj_valid.p + r0, e->st);
         if (err != hipSuccess)
             return fail(RC_E_HIP, std::string("nj_kernel (") + std::to_string(nj_lds_bytes(lds, n, W)) +
                                       " bytes of LDS): " + hipGetErrorString(err));
     }
-    launch_nj_support(e->d_nj_ref.p, n_ref, e->d_nj_splits.p, e->d_nj_valid.p, n_rep, n - 3, W, e->d_nj_sup.p,
-                      e->d_nj_sup.p + n_ref, e->st);
+    launch_nj_support(e->an.d_nj_ref.p, n_ref, e->an.d_nj_splits.p, e->an.d_nj_valid.p, n_rep, n - 3, W, e->an.d_nj_sup.p,
+                      e->an.d_nj_sup.p + n_ref, e->st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[15], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_NJ1], e->st));
     uint32_t nv = 0;
-    if (joins) HIPCHK(hipMemcpyAsync(joins, e->d_nj_joins.p, nj * 4, hipMemcpyDeviceToHost, e->st));
-    if (lengths) HIPCHK(hipMemcpyAsync(lengths, e->d_nj_len.p, nj * 8, hipMemcpyDeviceToHost, e->st));
-    if (splits && ns) HIPCHK(hipMemcpyAsync(splits, e->d_nj_splits.p, ns * 8, hipMemcpyDeviceToHost, e->st));
-    if (valid) HIPCHK(hipMemcpyAsync(valid, e->d_nj_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    if (joins) HIPCHK(hipMemcpyAsync(joins, e->an.d_nj_joins.p, nj * 4, hipMemcpyDeviceToHost, e->st));
+    if (lengths) HIPCHK(hipMemcpyAsync(lengths, e->an.d_nj_len.p, nj * 8, hipMemcpyDeviceToHost, e->st));
+    if (splits && ns) HIPCHK(hipMemcpyAsync(splits, e->an.d_nj_splits.p, ns * 8, hipMemcpyDeviceToHost, e->st));
+    if (valid) HIPCHK(hipMemcpyAsync(valid, e->an.d_nj_valid.p, R, hipMemcpyDeviceToHost, e->st));
     if (support && n_ref)
-        HIPCHK(hipMemcpyAsync(support, e->d_nj_sup.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(&nv, e->d_nj_sup.p + n_ref, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(support, e->an.d_nj_sup.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(&nv, e->an.d_nj_sup.p + n_ref, 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.nj_ms = ev_ms(e, 14, 15);
+    e->tm.nj_ms = ev_ms(e, EV_NJ0, EV_NJ1);
     if (n_valid) *n_valid = nv;
     *invalid = (uint32_t)n_rep - nv;
     return RC_OK;
@@ -303,10 +303,10 @@ int rc_nj(rc_engine *e, const double *D, int32_t n_rep, int32_t n, int32_t *join
     if (!D) return fail(RC_E_ARG, "null argument");
     CHK(set_device(e));
     const size_t nd = (size_t)n_rep * n * n;
-    CHK(e->d_nj_in.ensure(nd));
-    HIPCHK(hipMemcpyAsync(e->d_nj_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
+    CHK(e->an.d_nj_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->an.d_nj_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
     uint32_t invalid = 0;
-    CHK(nj_device(e, e->d_nj_in.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
+    CHK(nj_device(e, e->an.d_nj_in.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
                   &invalid));
     if (invalid) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no tree for it");
     return RC_OK;
@@ -322,7 +322,7 @@ int rc_resample_trees(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint
     uint32_t invalid = 0;
     CHK(nj_device(e, e->d_dist.p, n_rep, n, joins, lengths, splits, valid, ref_splits, n_ref, support, n_valid,
                   &invalid));
-    e->tm.resample_ms = ev_ms(e, 12, 13);
+    e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
     if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;
 }
@@ -348,8 +348,8 @@ static int pcoa_check(int32_t n_rep, int32_t n, int32_t k, int32_t max_sweeps)
 }
 
 // Eigenvalues and the first k eigenvectors of the n_rep matrices at dD
-// (device, n x n each); the arguments have passed pcoa_check. Events ev[16],
-// ev[17]. stat[0]: matrices with a non-finite entry or norm, stat[1]: matrices
+// (device, n x n each); the arguments have passed pcoa_check. Events EV_PCOA0,
+// EV_PCOA1. stat[0]: matrices with a non-finite entry or norm, stat[1]: matrices
 // that still rotated in their last allowed sweep.
 static int pcoa_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t k, int32_t max_sweeps,
                        double *values, double *vectors, int32_t *sweeps, uint8_t *valid, unsigned int stat[2])
@@ -360,26 +360,26 @@ static int pcoa_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n,
     HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
     if (pcoa_lds_bytes(n) + 4096 > (size_t)lds_max)
         return fail(RC_E_LIMIT, "this device's LDS does not hold a matrix of " + std::to_string(n) + " samples");
-    CHK(e->d_pcoa_val.ensure(nv));
-    CHK(e->d_pcoa_vec.ensure(nx));
-    CHK(e->d_pcoa_sweeps.ensure(R));
-    CHK(e->d_pcoa_valid.ensure(R));
-    CHK(e->d_pcoa_stat.ensure(2));
-    HIPCHK(hipMemsetAsync(e->d_pcoa_stat.p, 0, 2 * sizeof(unsigned int), e->st));
-    HIPCHK(hipEventRecord(e->ev[16], e->st));
-    const hipError_t err = launch_pcoa(dD, n_rep, n, k, max_sweeps, e->d_pcoa_val.p, e->d_pcoa_vec.p,
-                                       e->d_pcoa_sweeps.p, e->d_pcoa_valid.p, e->d_pcoa_stat.p, e->st);
+    CHK(e->an.d_pcoa_val.ensure(nv));
+    CHK(e->an.d_pcoa_vec.ensure(nx));
+    CHK(e->an.d_pcoa_sweeps.ensure(R));
+    CHK(e->an.d_pcoa_valid.ensure(R));
+    CHK(e->an.d_pcoa_stat.ensure(2));
+    HIPCHK(hipMemsetAsync(e->an.d_pcoa_stat.p, 0, 2 * sizeof(unsigned int), e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_PCOA0], e->st));
+    const hipError_t err = launch_pcoa(dD, n_rep, n, k, max_sweeps, e->an.d_pcoa_val.p, e->an.d_pcoa_vec.p,
+                                       e->an.d_pcoa_sweeps.p, e->an.d_pcoa_valid.p, e->an.d_pcoa_stat.p, e->st);
     if (err != hipSuccess)
         return fail(RC_E_HIP, std::string("pcoa_kernel (") + std::to_string(pcoa_lds_bytes(n)) +
                                   " bytes of LDS): " + hipGetErrorString(err));
-    HIPCHK(hipEventRecord(e->ev[17], e->st));
-    if (values) HIPCHK(hipMemcpyAsync(values, e->d_pcoa_val.p, nv * 8, hipMemcpyDeviceToHost, e->st));
-    if (vectors) HIPCHK(hipMemcpyAsync(vectors, e->d_pcoa_vec.p, nx * 8, hipMemcpyDeviceToHost, e->st));
-    if (sweeps) HIPCHK(hipMemcpyAsync(sweeps, e->d_pcoa_sweeps.p, R * 4, hipMemcpyDeviceToHost, e->st));
-    if (valid) HIPCHK(hipMemcpyAsync(valid, e->d_pcoa_valid.p, R, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(stat, e->d_pcoa_stat.p, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_PCOA1], e->st));
+    if (values) HIPCHK(hipMemcpyAsync(values, e->an.d_pcoa_val.p, nv * 8, hipMemcpyDeviceToHost, e->st));
+    if (vectors) HIPCHK(hipMemcpyAsync(vectors, e->an.d_pcoa_vec.p, nx * 8, hipMemcpyDeviceToHost, e->st));
+    if (sweeps) HIPCHK(hipMemcpyAsync(sweeps, e->an.d_pcoa_sweeps.p, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (valid) HIPCHK(hipMemcpyAsync(valid, e->an.d_pcoa_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(stat, e->an.d_pcoa_stat.p, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.pcoa_ms = ev_ms(e, 16, 17);
+    e->tm.pcoa_ms = ev_ms(e, EV_PCOA0, EV_PCOA1);
     return RC_OK;
 }
 
@@ -395,10 +395,10 @@ int rc_pcoa(rc_engine *e, const double *D, int32_t n_rep, int32_t n, int32_t k, 
     if (!D) return fail(RC_E_ARG, "null argument");
     CHK(set_device(e));
     const size_t nd = (size_t)n_rep * n * n;
-    CHK(e->d_pcoa_in.ensure(nd));
-    HIPCHK(hipMemcpyAsync(e->d_pcoa_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
+    CHK(e->an.d_pcoa_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->an.d_pcoa_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
     unsigned int stat[2] = {};
-    CHK(pcoa_device(e, e->d_pcoa_in.p, n_rep, n, k, max_sweeps, values, vectors, sweeps, valid, stat));
+    CHK(pcoa_device(e, e->an.d_pcoa_in.p, n_rep, n, k, max_sweeps, values, vectors, sweeps, valid, stat));
     if (stat[0]) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no ordination for it");
     if (stat[1]) return pcoa_unconverged();
     return RC_OK;
@@ -413,7 +413,7 @@ int rc_resample_pcoa(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint6
     CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
     unsigned int stat[2] = {};
     CHK(pcoa_device(e, e->d_dist.p, n_rep, n, k, max_sweeps, values, vectors, sweeps, valid, stat));
-    e->tm.resample_ms = ev_ms(e, 12, 13);
+    e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
     if (stat[0]) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     if (stat[1]) return pcoa_unconverged();
     return RC_OK;

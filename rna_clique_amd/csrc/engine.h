@@ -30,6 +30,8 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 using namespace rcg;
@@ -55,10 +57,33 @@ static inline int fail(int code, const std::string &msg) { return rcg_fail(code,
 void dev_account(long long b);
 
 // Device buffer that only grows (no allocation once sized: reruns are alloc-free).
+// It owns its allocation: moved and swapped, never copied. A move or a swap
+// accounts for nothing (dev_account); a moved-from buffer is empty.
 template <class T>
 struct DBuf {
     T *p = nullptr;
     size_t cap = 0;
+    DBuf() = default;
+    DBuf(const DBuf &) = delete;
+    DBuf &operator=(const DBuf &) = delete;
+    DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap)
+    {
+        o.p = nullptr;
+        o.cap = 0;
+    }
+    DBuf &operator=(DBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            swap(o);
+        }
+        return *this;
+    }
+    void swap(DBuf &o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
     int ensure(size_t n)
     {
         if (n <= cap && p) return RC_OK;
@@ -97,6 +122,9 @@ struct DBuf {
         cap = 0;
     }
 };
+static_assert(!std::is_copy_constructible<DBuf<int>>::value && !std::is_copy_assignable<DBuf<int>>::value,
+              "a copy would free and account for the allocation twice");
+static_assert(std::is_nothrow_move_constructible<DBuf<int>>::value, "moves only take the pointer over");
 
 // engine.hip: Karlin-Altschul statistics
 namespace stats {
@@ -137,6 +165,37 @@ struct Knobs {
     int resume;           // RC_RESUME (unset = -1: by the last run's overflows): 1 = always save 32-lane states, 0 = never
     uint32_t index_cap;   // RC_INDEX_CAP (unset = 0: the local sort's capacity; else at least 2): main-index ranges of more keys count as oversized (tests: the fallbacks)
     int nj_lds;           // RC_NJ_LDS (128; at most 128): the most samples whose neighbour-joining matrix lives in LDS; 0 = every tree through the global workspace (tests: that path)
+};
+
+// The engine's timing events (rc_engine::ev, on stream st), each named by what
+// its record marks; a pair brackets one rc_timing field (ev_ms). The values
+// are the order in which the events were added. External HSPs run no tile, so
+// no stage records EV_PACK0 and EV_INDEX0 then: do_align_tiles reuses the two
+// to bracket load_external (align_ms).
+enum Ev {
+    EV_PACK0 = 0,     // pack_tile: the packing starts (pack_ms to EV_INDEX0)
+    EV_INDEX0 = 1,    // index_stage: packed, masks cleared; DUST and the index build start (index_ms to EV_ALIGN0)
+    EV_ALIGN0 = 2,    // index_stage: indexes done (align_ms to EV_GROUPS1)
+    EV_SEED0 = 3,     // seed_stage: before the reverse pass and the seed launches (seed_kernel_ms to EV_SEED1)
+    EV_GROUPS1 = 4,   // group_stage: the tile's HSP groups are written
+    EV_RBH0 = 5,      // do_rbh (rbh_ms to EV_GRAPH0)
+    EV_GRAPH0 = 6,    // do_rbh: rows and edges placed; recorded again when do_graph starts (graph_ms to EV_REDUCE0)
+    EV_REDUCE0 = 7,   // do_graph: components and ideal filter done (reduce_ms to EV_REDUCE1)
+    EV_REDUCE1 = 8,   // do_graph: pair sums copied back
+    EV_SEED1 = 9,     // seed_stage: an attempt's last seed launch
+    EV_EXTEND0 = 10,  // extension_stage: before the row kernels (align_kernel_ms to EV_EXTEND1)
+    EV_EXTEND1 = 11,  // extension_stage: after extend_kernel
+    EV_RESAMPLE0 = 12, EV_RESAMPLE1 = 13,   // resample_fill: the replicate sums (resample_ms)
+    EV_NJ0 = 14, EV_NJ1 = 15,               // nj_device: the trees and the split support (nj_ms)
+    EV_PCOA0 = 16, EV_PCOA1 = 17,           // pcoa_device: the ordinations (pcoa_ms)
+    EV_N
+};
+// rc_engine::evd: DUST on the second stream
+enum Evd {
+    EVD_DUST0 = 0,   // on st2: DUST starts
+    EVD_DUST1 = 1,   // on st2: DUST ends (st waits for it; dust_ms from EVD_DUST0)
+    EVD_READY = 2,   // on st: DUST's start condition (the packed copy, the cleared masks)
+    EVD_N
 };
 
 struct rc_engine {
@@ -182,7 +241,6 @@ struct rc_engine {
     };
     std::vector<Tile> tiles;
     int64_t tiles_for = -1;
-    int tile_loaded = -1;
     std::vector<uint64_t> tile_pos;     // first base of each sample in the loaded tile
     uint64_t tile_total = 0;
     bool tile_direct = false;           // the loaded tile is d_ascii's layout (no gathered copy)
@@ -195,10 +253,6 @@ struct rc_engine {
     // after an rc_dust_masks pass over the loaded tile itself: which samples'
     // masks it recomputed (the others were cleared); empty = every tile sample
     std::vector<char> dmask_only;
-    // the b chunk (split tiles) whose index and DUST masks the device holds
-    // from this run's previous tile (-1: none)
-    int idx_bchunk = -1;
-    uint64_t idx_bstart = 0;
     uint64_t hsp_used = 0;              // HSPs appended to d_hsp by the tiles of this run
 
     // external HSPs
@@ -214,136 +268,175 @@ struct rc_engine {
     bool graph_only = false;        // an imported graph + tables, no alignment (rc_import_edges on a fresh engine)
     int32_t sample_count_given = 0; // > 0: the ideal test's sample count (rc_set_sample_count)
 
-    // device buffers
-    DBuf<uint8_t> d_ascii, d_tile_ascii;
-    DBuf<TxInfo> d_tile_tx, d_tile_itx;
-    DBuf<uint32_t> d_tile_gid;          // global id of each tile transcript
-    DBuf<TileSeg> d_tile_segs;
-    DBuf<uint64_t> d_tile_send, d_tx_rel, d_kpre;   // tile sample ends; per transcript: start in its sample,
-                                                    // 16-mer slots of its sample's transcripts before it
-    DBuf<uint64_t> d_F, d_RC, d_AF, d_ARC;
-    DBuf<TxInfo> d_tx;
-    DBuf<IsoRec> d_giso;
-    DBuf<uint32_t> d_tx_gene, d_gene_tx_off, d_gene_tx, d_sample_gene_begin, d_sample_tx_begin;
-    DBuf<int32_t> d_gene_sample;
-    DBuf<uint64_t> d_kpos_off, d_kcnt;
-    // shared searches with DUST: masked tile transcripts, the near-mask index
-    // of the reverse pass, its reverse-only seeds (sorted by forward gene)
-    DBuf<uint8_t> d_tile_masked;
-    DBuf<uint64_t> d_ment, d_ment2;
-    DBuf<uint32_t> d_mbucket;
-    int mindex_bits = 16;
-    uint64_t n_mindex = 0, mnear_cap = 0;
-    DBuf<LSeed> d_rseeds;
-    DBuf<uint32_t> d_rseed_gene, d_rs_key, d_rs_idx, d_rs_range;
-    DBuf<unsigned long long> d_rctr;   // [0] near-index entries, [1] reverse-only seeds
-    DBuf<uint64_t> d_rtmask;
-    DBuf<int32_t> d_trange, d_rtrange;   // [N][2] subject-sample range of each query sample (tmask / rtmask)
-    uint64_t rseed_cap = 0, n_rseeds = 0;
-    uint32_t res_cap = 0;
-    // fraction of the last run's candidates whose first-seed extension
-    // outgrew the 32-lane window (selects the saving row kernel, RC_RESUME)
-    double ovf_frac = 0.0;
-    DBuf<uint64_t> d_ent, d_ent2;   // (k-mer << 32 | position), unsorted / sorted
-    // the index sort's scratch (sort.hip): digit histograms + tile counters,
-    // the look-back table (zeroed when allocated; tagged by pass epoch)
-    DBuf<uint32_t> d_sort_scratch;
-    DBuf<uint64_t> d_sort_status;
-    uint32_t sort_epoch = 0;
-    // the main index's range offsets (2^G + 1) and its list of oversized ranges
-    DBuf<uint32_t> d_range_off, d_range_list;
-    DBuf<uint32_t> d_bucket;
-    DBuf<PosTx> d_pos_tx;
-    DBuf<uint64_t> d_sample_pos, d_txstart, d_kpos_rel, d_dmask, d_dust_imp;
-    DBuf<uint32_t> d_dust_scratch;
-    DBuf<uint64_t> d_dust_events;
-    DBuf<unsigned long long> d_prof;
-    DBuf<uint8_t> d_tmp;
-    DBuf<int32_t> d_thr, d_bits10;
-    DBuf<DHsp> d_hsp;
-    DBuf<HKey> d_hkey;   // RBH: (bit score, subject gene) per d_hsp entry
-    DBuf<GSeed> d_seeds;
-    DBuf<Cand> d_cands;
-    DBuf<DHsp> d_cand_hsp, d_ovf;
-    DBuf<uint8_t> d_cand_nh;
-    DBuf<int32_t> d_cand_box, d_cand_box2;
-    // shared searches (RC_SHARE, default): the reverse search's HSPs per candidate
-    DBuf<DHsp> d_cand_hsp_r;
-    DBuf<uint8_t> d_cand_nh_r;
-    DBuf<uint32_t> d_cand_ovf_r, d_defer_r, d_list2, d_wide0, d_wide1;
-    DBuf<int32_t> d_resume;   // saved 32-lane extension states for the 64-lane pass (RES_REC ints each)
-    // later-seed rounds (shared searches): search states, the rounds' work
-    // (alternating), active lists, counters
-    DBuf<int32_t> d_later, d_lbox0, d_lbox1;
-    DBuf<Cand> d_lvc0, d_lvc1;
-    DBuf<uint32_t> d_llist0, d_llist1, d_lact0, d_lact1, d_lfull0, d_lfull1;
-    DBuf<unsigned long long> d_lcnt;
     // both directed searches of a pair from one candidate set (query = the
     // lower sample), unless spec 5b or RC_SHARE=0 (one after
     // the other); fixed when the engine is created
     bool share = false;
-    DBuf<DRow> d_rows_tmp;
-    DBuf<DEdge> d_edges_tmp;
-    DBuf<uint32_t> d_cand_ovf, d_gc_off, d_gc_cnt, d_gcount, d_defer;
-    DBuf<uint64_t> d_gscan, d_mscan, d_mkey, d_tmask, d_mbig;
-    DBuf<uint32_t> d_mcnt, d_mcur, d_tx_pos, d_iso_pre, d_iso_list, d_iso_list_r;
-    DBuf<unsigned long long> d_shard_cnt, d_shard_prefix;
+    // capacities and cursors that outlive a run (rc_trim keeps them: they
+    // select the next run's first guesses and retry paths)
+    int mindex_bits = 16;
+    uint64_t n_mindex = 0;
+    uint64_t rseed_cap = 0, n_rseeds = 0;
+    // fraction of the last run's candidates whose first-seed extension
+    // outgrew the 32-lane window (selects the saving row kernel, RC_RESUME)
+    double ovf_frac = 0.0;
+    uint32_t sort_epoch = 0;   // the index sort's pass counter (tags d_sort_status)
     uint64_t seed_cap = 0, cand_cap = 0, ovf_cap = 0;   // per-shard / total capacities
-    // (gene, sample) seed passes too big for LDS, and their global scratch
-    DBuf<uint64_t> d_big_out, d_big_list, d_big_retry;
-    DBuf<LSeed> d_big_seeds;
-    DBuf<uint32_t> d_big_seg;
-    DBuf<uint8_t> d_big_segT;
     uint64_t big_list_cap = 1 << 16;
     uint32_t big_cap = 1 << 13;
-    DBuf<uint32_t> d_grp_off, d_grp_cnt;
-    DBuf<unsigned long long> d_count;
-    DBuf<unsigned int> d_status;
+    // what the last run produced
+    uint64_t n_rows = 0, n_edges = 0, n_hsps = 0, n_seeds = 0, n_cands = 0;
+
+    // The alignment working set: what only rc_align (and rc_finish's RBH pass)
+    // fills and reads, with the scalars that describe what these buffers hold.
+    // rc_trim frees it whole (work = Work{}); the next rc_align allocates it
+    // again. A finished run's results need none of it. (hidden, like Analysis:
+    // the library exports none of the members the compiler generates for it)
+    struct __attribute__((visibility("hidden"))) Work {
+        int tile_loaded = -1;   // the tile whose tables are on the device (rc_dust_masks reads a loaded tile)
+        // the b chunk (split tiles) whose index and DUST masks the device holds
+        // from this run's previous tile (-1: none)
+        int idx_bchunk = -1;
+        uint64_t idx_bstart = 0;
+        DBuf<uint8_t> d_tile_ascii;
+        DBuf<TxInfo> d_tile_tx, d_tile_itx;
+        DBuf<uint32_t> d_tile_gid;          // global id of each tile transcript
+        DBuf<TileSeg> d_tile_segs;
+        DBuf<uint64_t> d_tile_send;         // tile sample ends
+        DBuf<uint64_t> d_F, d_RC, d_AF, d_ARC;
+        DBuf<uint64_t> d_kpos_off, d_kcnt;
+        // shared searches with DUST: masked tile transcripts, the near-mask index
+        // of the reverse pass, its reverse-only seeds (sorted by forward gene)
+        DBuf<uint8_t> d_tile_masked;
+        DBuf<uint64_t> d_ment, d_ment2;
+        DBuf<uint32_t> d_mbucket;
+        uint64_t mnear_cap = 0;
+        DBuf<LSeed> d_rseeds;
+        DBuf<uint32_t> d_rseed_gene, d_rs_key, d_rs_idx, d_rs_range;
+        DBuf<unsigned long long> d_rctr;   // [0] near-index entries, [1] reverse-only seeds
+        DBuf<uint64_t> d_rtmask;
+        DBuf<int32_t> d_trange, d_rtrange;   // [N][2] subject-sample range of each query sample (tmask / rtmask)
+        uint32_t res_cap = 0;              // extensions d_resume has room for
+        DBuf<uint64_t> d_ent, d_ent2;   // (k-mer << 32 | position), unsorted / sorted
+        // the index sort's scratch (sort.hip): digit histograms + tile counters,
+        // the look-back table (zeroed when allocated; tagged by pass epoch)
+        DBuf<uint32_t> d_sort_scratch;
+        DBuf<uint64_t> d_sort_status;
+        // the main index's range offsets (2^G + 1) and its list of oversized ranges
+        DBuf<uint32_t> d_range_off, d_range_list;
+        DBuf<uint32_t> d_bucket;
+        DBuf<PosTx> d_pos_tx;
+        DBuf<uint64_t> d_sample_pos, d_txstart, d_kpos_rel, d_dmask;
+        DBuf<uint32_t> d_dust_scratch;
+        DBuf<uint64_t> d_dust_events;
+        DBuf<unsigned long long> d_prof;
+        // rocPRIM's temporary storage: the result and analysis calls size it
+        // again when they need it
+        DBuf<uint8_t> d_tmp;
+        DBuf<HKey> d_hkey;   // RBH: (bit score, subject gene) per d_hsp entry
+        DBuf<GSeed> d_seeds;
+        DBuf<Cand> d_cands;
+        DBuf<DHsp> d_cand_hsp, d_ovf;
+        DBuf<uint8_t> d_cand_nh;
+        DBuf<int32_t> d_cand_box, d_cand_box2;
+        // shared searches (RC_SHARE, default): the reverse search's HSPs per candidate
+        DBuf<DHsp> d_cand_hsp_r;
+        DBuf<uint8_t> d_cand_nh_r;
+        DBuf<uint32_t> d_cand_ovf_r, d_defer_r, d_list2, d_wide0, d_wide1;
+        DBuf<int32_t> d_resume;   // saved 32-lane extension states for the 64-lane pass (RES_REC ints each)
+        // later-seed rounds (shared searches): search states, the rounds' work
+        // (alternating), active lists, counters
+        DBuf<int32_t> d_later, d_lbox0, d_lbox1;
+        DBuf<Cand> d_lvc0, d_lvc1;
+        DBuf<uint32_t> d_llist0, d_llist1, d_lact0, d_lact1, d_lfull0, d_lfull1;
+        DBuf<unsigned long long> d_lcnt;
+        DBuf<DRow> d_rows_tmp;
+        DBuf<DEdge> d_edges_tmp;
+        DBuf<uint32_t> d_cand_ovf, d_gc_off, d_gc_cnt, d_gcount, d_defer;
+        DBuf<uint64_t> d_gscan, d_mscan, d_mkey, d_tmask, d_mbig;
+        DBuf<uint32_t> d_mcnt, d_mcur;
+        // (gene, sample) seed passes too big for LDS, and their global scratch
+        DBuf<uint64_t> d_big_out, d_big_list, d_big_retry;
+        DBuf<LSeed> d_big_seeds;
+        DBuf<uint32_t> d_big_seg;
+        DBuf<uint8_t> d_big_segT;
+        DBuf<uint32_t> d_cnt4;   // 4 * (n_items + 1)
+    };
+    Work work;
+
+    // What analysis.hip alone owns. The per-component tables (components.hip)
+    // are built by the first call that needs them after a graph phase and
+    // dropped by the next one (do_graph clears comp_valid): rank of each gene's
+    // ideal[] prefix, members [C][S], sums [C][P] and their 32-bit copy.
+    // rc_trim keeps all of it.
+    struct __attribute__((visibility("hidden"))) Analysis {
+        bool comp_valid = false;
+        uint64_t comp_n = 0, comp_max_cell = 0;
+        uint32_t comp_S = 0;
+        DBuf<uint32_t> d_crank, d_cmember;
+        DBuf<unsigned long long> d_cnum, d_cden, d_cstat, d_rnum, d_rden;
+        DBuf<uint2> d_ccell;
+        DBuf<uint16_t> d_rweight;
+        // neighbour joining (nj.hip): input matrices of rc_nj, the trees, the
+        // reference splits with their support (n_ref counters, then n_valid) and
+        // the workspace of the trees too large for LDS
+        DBuf<double> d_nj_in, d_nj_len, d_nj_wsm;
+        DBuf<int32_t> d_nj_joins;
+        DBuf<uint64_t> d_nj_splits, d_nj_ref, d_nj_wsmask;
+        DBuf<uint8_t> d_nj_valid;
+        DBuf<uint32_t> d_nj_sup;
+        // principal coordinates (pcoa.hip): input matrices of rc_pcoa, the results
+        // and the status words (invalid, unconverged replicates)
+        DBuf<double> d_pcoa_in, d_pcoa_val, d_pcoa_vec;
+        DBuf<int32_t> d_pcoa_sweeps;
+        DBuf<uint8_t> d_pcoa_valid;
+        DBuf<unsigned int> d_pcoa_stat;
+    };
+    Analysis an;
+
+    // device buffers, resident from upload (rc_add_sample, upload,
+    // rc_set_dust_masks): they live as long as the samples
+    DBuf<uint8_t> d_ascii;
+    DBuf<uint64_t> d_tx_rel, d_kpre;   // per transcript: start in its sample,
+                                       // 16-mer slots of its sample's transcripts before it
+    DBuf<TxInfo> d_tx;
+    DBuf<IsoRec> d_giso;
+    DBuf<uint32_t> d_tx_gene, d_gene_tx_off, d_gene_tx, d_sample_gene_begin, d_sample_tx_begin;
+    DBuf<int32_t> d_gene_sample;
+    DBuf<uint64_t> d_dust_imp;
+    DBuf<int32_t> d_thr, d_bits10;
+    DBuf<uint32_t> d_tx_pos, d_iso_pre;
     DBuf<uint32_t> d_pair_item_begin;
     DBuf<int32_t> d_pair_a, d_pair_b, d_pair_index;
-    DBuf<uint32_t> d_cnt4;   // 4 * (n_items + 1)
+
+    // device buffers, results of a finished run (rc_trim keeps them)
+    DBuf<DHsp> d_hsp;
+    DBuf<uint32_t> d_grp_off, d_grp_cnt;
     DBuf<uint64_t> d_off4;   // 4 * (n_items + 1)
     DBuf<DRow> d_rows;
-    DBuf<DHsp> d_gather;
     DBuf<DEdge> d_edges;
-    uint64_t n_rows = 0, n_edges = 0, n_hsps = 0, n_seeds = 0, n_cands = 0;
     DBuf<uint32_t> d_parent, d_present, d_cnodes, d_cedges, d_sample_present;
     DBuf<uint8_t> d_ideal;
     DBuf<unsigned long long> d_stats, d_num, d_den, d_num_all, d_den_all;
+
+    // device buffers, shared scratch: small, or reused by the result and
+    // analysis calls (d_iso_list, d_iso_list_r, d_shard_cnt, d_shard_prefix and
+    // d_count are rc_align's alone, yet rc_trim keeps them)
+    DBuf<uint32_t> d_iso_list, d_iso_list_r;
+    DBuf<unsigned long long> d_shard_cnt, d_shard_prefix;
+    DBuf<unsigned long long> d_count;
+    DBuf<unsigned int> d_status;
+    DBuf<DHsp> d_gather;
     DBuf<int32_t> d_order;
     DBuf<double> d_dist;
-    // per-component tables (components.hip), built by the first call that
-    // needs them after a graph phase and dropped by the next one: rank of each
-    // gene's ideal[] prefix, members [C][S], sums [C][P] and their 32-bit copy
-    bool comp_valid = false;
-    uint64_t comp_n = 0, comp_max_cell = 0;
-    uint32_t comp_S = 0;
-    DBuf<uint32_t> d_crank, d_cmember;
-    DBuf<unsigned long long> d_cnum, d_cden, d_cstat, d_rnum, d_rden;
-    DBuf<uint2> d_ccell;
-    DBuf<uint16_t> d_rweight;
-    // neighbour joining (nj.hip): input matrices of rc_nj, the trees, the
-    // reference splits with their support (n_ref counters, then n_valid) and
-    // the workspace of the trees too large for LDS
-    DBuf<double> d_nj_in, d_nj_len, d_nj_wsm;
-    DBuf<int32_t> d_nj_joins;
-    DBuf<uint64_t> d_nj_splits, d_nj_ref, d_nj_wsmask;
-    DBuf<uint8_t> d_nj_valid;
-    DBuf<uint32_t> d_nj_sup;
-    // principal coordinates (pcoa.hip): input matrices of rc_pcoa, the results
-    // and the status words (invalid, unconverged replicates)
-    DBuf<double> d_pcoa_in, d_pcoa_val, d_pcoa_vec;
-    DBuf<int32_t> d_pcoa_sweeps;
-    DBuf<uint8_t> d_pcoa_valid;
-    DBuf<unsigned int> d_pcoa_stat;
 
     // host results
     std::vector<unsigned long long> h_num, h_den, h_num_all, h_den_all, h_stats;
     std::vector<double> h_ss;   // search space of a query of length L against sample T: [T][L]
     std::vector<double> h_exp;  // exp(-lambda * S / 2) per raw score in half units S (stats::evalue's factor)
     rc_timing tm{};
-    hipEvent_t ev[18] = {};
-    hipEvent_t evd[3] = {};   // DUST start / end on st2, its start condition on st
+    hipEvent_t ev[EV_N] = {};
+    hipEvent_t evd[EVD_N] = {};
 
     ~rc_engine()
     {

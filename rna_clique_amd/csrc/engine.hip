@@ -585,7 +585,7 @@ static int upload(rc_engine *e)
     CHK(e->d_status.ensure(4));
     CHK(e->d_count.ensure(DC_N));
     HIPCHK(hipStreamSynchronize(e->st));
-    e->tile_loaded = -1;
+    e->work.tile_loaded = -1;
     e->uploaded = true;
     return RC_OK;
 }
@@ -714,7 +714,7 @@ static int load_tile(rc_engine *e, int ti)
     // the 16-mer index holds the tile's subject samples only: the b of each
     // pair (shared searches and spec 5b: query = the lower sample), or both
     const bool share = e->share;
-    if (e->tile_loaded == ti) return RC_OK;
+    if (e->work.tile_loaded == ti) return RC_OK;
     std::vector<char> subj(N, 0);
     for (auto &pr : T.pairs) {
         subj[pr.second] = 1;
@@ -765,23 +765,24 @@ static int load_tile(rc_engine *e, int ti)
     e->tile_tx_first[N] = n_ttx;
     if (npos > 0xFFFFFFFFull) return fail(RC_E_LIMIT, "more than 2^32 seed positions in a tile");
     const uint64_t nblocks = (total >> POS_TX_SHIFT) + 2, nwb = (total >> 6) + 4;
-    CHK(e->d_tile_segs.ensure(std::max<size_t>(segs.size(), 1)));
-    CHK(e->d_tile_tx.ensure(std::max<uint32_t>(n_ttx, 1)));
-    CHK(e->d_tile_gid.ensure(std::max<uint32_t>(n_ttx, 1)));
-    CHK(e->d_tile_itx.ensure(std::max<uint32_t>(n_itx, 1)));
-    CHK(e->d_kpos_off.ensure((size_t)n_itx + 1));
-    CHK(e->d_pos_tx.ensure(nblocks));
-    CHK(e->d_sample_pos.ensure(spos.size()));
-    CHK(e->d_tile_send.ensure(send.size()));
-    CHK(e->d_txstart.ensure(nwb));
+    CHK(e->work.d_tile_segs.ensure(std::max<size_t>(segs.size(), 1)));
+    CHK(e->work.d_tile_tx.ensure(std::max<uint32_t>(n_ttx, 1)));
+    CHK(e->work.d_tile_gid.ensure(std::max<uint32_t>(n_ttx, 1)));
+    CHK(e->work.d_tile_itx.ensure(std::max<uint32_t>(n_itx, 1)));
+    CHK(e->work.d_kpos_off.ensure((size_t)n_itx + 1));
+    CHK(e->work.d_pos_tx.ensure(nblocks));
+    CHK(e->work.d_sample_pos.ensure(spos.size()));
+    CHK(e->work.d_tile_send.ensure(send.size()));
+    CHK(e->work.d_txstart.ensure(nwb));
     if (!segs.empty())
-        HIPCHK(hipMemcpyAsync(e->d_tile_segs.p, segs.data(), segs.size() * sizeof(TileSeg), hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemcpyAsync(e->d_sample_pos.p, spos.data(), spos.size() * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemcpyAsync(e->d_tile_send.p, send.data(), send.size() * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemsetAsync(e->d_txstart.p, 0, nwb * 8, e->st));
-    launch_tile_tables(e->d_tile_segs.p, (uint32_t)segs.size(), n_ttx, e->d_tx_rel.p, e->d_kpre.p, e->d_tx.p,
-                       e->d_tile_tx.p, e->d_tile_gid.p, e->d_tile_itx.p, e->d_kpos_off.p, n_itx, npos,
-                       e->d_txstart.p, e->d_giso.p, e->gene_tx.size(), e->d_tile_send.p, e->d_pos_tx.p, nblocks,
+        HIPCHK(hipMemcpyAsync(e->work.d_tile_segs.p, segs.data(), segs.size() * sizeof(TileSeg), hipMemcpyHostToDevice,
+                              e->st));
+    HIPCHK(hipMemcpyAsync(e->work.d_sample_pos.p, spos.data(), spos.size() * 8, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemcpyAsync(e->work.d_tile_send.p, send.data(), send.size() * 8, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemsetAsync(e->work.d_txstart.p, 0, nwb * 8, e->st));
+    launch_tile_tables(e->work.d_tile_segs.p, (uint32_t)segs.size(), n_ttx, e->d_tx_rel.p, e->d_kpre.p, e->d_tx.p,
+                       e->work.d_tile_tx.p, e->work.d_tile_gid.p, e->work.d_tile_itx.p, e->work.d_kpos_off.p, n_itx, npos,
+                       e->work.d_txstart.p, e->d_giso.p, e->gene_tx.size(), e->work.d_tile_send.p, e->work.d_pos_tx.p, nblocks,
                        e->st);
     HIPCHK(hipGetLastError());
     e->tile_npos = npos;
@@ -789,16 +790,16 @@ static int load_tile(rc_engine *e, int ti)
     e->tile_nitx = n_itx;
     // the packed working copy's source: d_ascii itself or a gathered copy
     if (!direct) {
-        CHK(e->d_tile_ascii.ensure(total + 64));
-        HIPCHK(hipMemsetAsync(e->d_tile_ascii.p, 'A', total + 64, e->st));
+        CHK(e->work.d_tile_ascii.ensure(total + 64));
+        HIPCHK(hipMemsetAsync(e->work.d_tile_ascii.p, 'A', total + 64, e->st));
         for (int s = 0; s < N; s++)
             if (in[s] && e->samples[s].nbases)
-                HIPCHK(hipMemcpyAsync(e->d_tile_ascii.p + e->tile_pos[s], e->d_ascii.p + e->samples[s].abase,
+                HIPCHK(hipMemcpyAsync(e->work.d_tile_ascii.p + e->tile_pos[s], e->d_ascii.p + e->samples[s].abase,
                                       e->samples[s].nbases, hipMemcpyDeviceToDevice, e->st));
     }
     // (no wait: the host tables above are engine members, kept until the
     // next load, which comes after this tile's last wait)
-    e->tile_loaded = ti;
+    e->work.tile_loaded = ti;
     return RC_OK;
 }
 
@@ -829,23 +830,23 @@ static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, u
     if (npos) {
         // the result must end in ent2
         if (npos > 0xFFFFFFFFull) return fail(RC_E_LIMIT, "more than 2^32 index entries");
-        CHK(e->d_sort_scratch.ensure(G >= 0 ? os_index_scratch_words(npos) : os_scratch_words(npos)));
+        CHK(e->work.d_sort_scratch.ensure(G >= 0 ? os_index_scratch_words(npos) : os_scratch_words(npos)));
         const uint64_t words = G >= 0 ? os_index_status_words(npos) : os_status_words(npos);
-        if (e->d_sort_status.cap < words) {
-            CHK(e->d_sort_status.ensure(words));
-            HIPCHK(hipMemsetAsync(e->d_sort_status.p, 0, words * sizeof(uint64_t), e->st));
+        if (e->work.d_sort_status.cap < words) {
+            CHK(e->work.d_sort_status.ensure(words));
+            HIPCHK(hipMemsetAsync(e->work.d_sort_status.p, 0, words * sizeof(uint64_t), e->st));
         }
         bool in_alt;
         if (G >= 0) {
-            CHK(e->d_range_off.ensure(os_index_offset_words(G)));
-            CHK(e->d_range_list.ensure(os_index_list_words()));
+            CHK(e->work.d_range_off.ensure(os_index_offset_words(G)));
+            CHK(e->work.d_range_list.ensure(os_index_list_words()));
             uint32_t fb_ranges = 0;
             uint64_t fb_keys = 0;
             bool whole = false;
-            const int where = os_index_sort(ent.p, ent2.p, npos, G, bits, e->knobs.index_cap, e->d_sort_scratch.p,
-                                            e->d_sort_status.p, e->sort_epoch, e->d_range_off.p, e->d_range_list.p,
-                                            bucket.p, e->st, counted, [e] { return wait_st(e) == RC_OK; }, &fb_ranges,
-                                            &fb_keys, &whole);
+            const int where = os_index_sort(ent.p, ent2.p, npos, G, bits, e->knobs.index_cap, e->work.d_sort_scratch.p,
+                                            e->work.d_sort_status.p, e->sort_epoch, e->work.d_range_off.p,
+                                            e->work.d_range_list.p, bucket.p, e->st, counted,
+                                            [e] { return wait_st(e) == RC_OK; }, &fb_ranges, &fb_keys, &whole);
             if (where < 0) return fail(RC_E_HIP, "the index sort's read of its oversized ranges failed");
             in_alt = where == 1;
             table_done = !whole;
@@ -853,14 +854,11 @@ static int sort_index(rc_engine *e, DBuf<uint64_t> &ent, DBuf<uint64_t> &ent2, u
             e->tm.index_fb_keys += (double)fb_keys;
         } else {
             // (no callback after the table kernels, no key generator: keys come from the entry array)
-            in_alt = os_sort_keys(ent.p, ent2.p, npos, (int)bb, e->d_sort_scratch.p, e->d_sort_status.p,
+            in_alt = os_sort_keys(ent.p, ent2.p, npos, (int)bb, e->work.d_sort_scratch.p, e->work.d_sort_status.p,
                                   e->sort_epoch, e->st, nullptr, counted, nullptr, nullptr, nullptr, 0u, nullptr);
         }
         HIPCHK(hipGetLastError());
-        if (!in_alt) {
-            std::swap(ent.p, ent2.p);
-            std::swap(ent.cap, ent2.cap);
-        }
+        if (!in_alt) ent.swap(ent2);
     }
     if (!table_done) launch_bucket_fill(ent2.p, npos, bits, bucket.p, e->st);
     return RC_OK;
@@ -875,19 +873,19 @@ static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64
     const bool amb = e->has_amb;
     const uint64_t *offs = kpos;
     if (amb) {
-        CHK(e->d_kcnt.ensure(n_tx + 1));
-        HIPCHK(hipMemsetAsync(e->d_kcnt.p, 0, (n_tx + 1) * sizeof(uint64_t), e->st));
-        if (n_tx) launch_kmer_count(txl, n_tx, e->d_AF.p + FRONT_PAD, e->d_kcnt.p, e->st);
+        CHK(e->work.d_kcnt.ensure(n_tx + 1));
+        HIPCHK(hipMemsetAsync(e->work.d_kcnt.p, 0, (n_tx + 1) * sizeof(uint64_t), e->st));
+        if (n_tx) launch_kmer_count(txl, n_tx, e->work.d_AF.p + FRONT_PAD, e->work.d_kcnt.p, e->st);
         size_t tmp = 0;
-        CHK(e->d_kpos_rel.ensure(n_tx + 1));
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->d_kcnt.p, e->d_kpos_rel.p, (uint64_t)0, (size_t)n_tx + 1,
+        CHK(e->work.d_kpos_rel.ensure(n_tx + 1));
+        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->work.d_kcnt.p, e->work.d_kpos_rel.p, (uint64_t)0, (size_t)n_tx + 1,
                                        rocprim::plus<uint64_t>(), e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::exclusive_scan(e->d_tmp.p, tmp, e->d_kcnt.p, e->d_kpos_rel.p, (uint64_t)0,
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->work.d_tmp.p, tmp, e->work.d_kcnt.p, e->work.d_kpos_rel.p, (uint64_t)0,
                                        (size_t)n_tx + 1, rocprim::plus<uint64_t>(), e->st));
-        HIPCHK(hipMemcpyAsync(&npos, e->d_kpos_rel.p + n_tx, sizeof(uint64_t), hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&npos, e->work.d_kpos_rel.p + n_tx, sizeof(uint64_t), hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
-        offs = e->d_kpos_rel.p;
+        offs = e->work.d_kpos_rel.p;
     }
     CHK(ent.ensure(std::max<uint64_t>(npos, 1)));
     CHK(ent2.ensure(std::max<uint64_t>(npos, 1)));
@@ -898,13 +896,13 @@ static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64
     // (G < 0: too many entries for ranges that fit the local sort; the 8-bit passes)
     const int G = os_index_gbits(npos, index_bits(npos, 0), e->knobs.index_cap);
     if (counted && G >= 0) {
-        CHK(e->d_sort_scratch.ensure(os_index_scratch_words(npos)));
-        os_index_fill_hist(txl, n_tx, e->d_F.p + FRONT_PAD, offs, ent.p, npos, G, e->d_sort_scratch.p, e->st);
+        CHK(e->work.d_sort_scratch.ensure(os_index_scratch_words(npos)));
+        os_index_fill_hist(txl, n_tx, e->work.d_F.p + FRONT_PAD, offs, ent.p, npos, G, e->work.d_sort_scratch.p, e->st);
     } else if (counted) {
-        CHK(e->d_sort_scratch.ensure(os_scratch_words(npos)));
-        os_fill_hist(txl, n_tx, e->d_F.p + FRONT_PAD, offs, ent.p, npos, e->d_sort_scratch.p, e->st);
+        CHK(e->work.d_sort_scratch.ensure(os_scratch_words(npos)));
+        os_fill_hist(txl, n_tx, e->work.d_F.p + FRONT_PAD, offs, ent.p, npos, e->work.d_sort_scratch.p, e->st);
     } else if (n_tx) {
-        launch_kmer_fill(amb, txl, n_tx, e->d_F.p + FRONT_PAD, amb ? e->d_AF.p + FRONT_PAD : nullptr, offs, ent.p,
+        launch_kmer_fill(amb, txl, n_tx, e->work.d_F.p + FRONT_PAD, amb ? e->work.d_AF.p + FRONT_PAD : nullptr, offs, ent.p,
                          e->st);
     }
     // sort on the k-mer (bits 32..63); the fill order is position order and the
@@ -917,8 +915,8 @@ static int build_index_of(rc_engine *e, const TxInfo *txl, uint32_t n_tx, uint64
 // The seed index of the loaded tile: every 16-mer position of its subject samples' transcripts.
 static int build_index(rc_engine *e)
 {
-    return build_index_of(e, e->d_tile_itx.p, e->tile_nitx, e->tile_npos, e->d_kpos_off.p, e->d_ent,
-                          e->d_ent2, e->d_bucket, e->index_bits, e->n_index);
+    return build_index_of(e, e->work.d_tile_itx.p, e->tile_nitx, e->tile_npos, e->work.d_kpos_off.p, e->work.d_ent,
+                          e->work.d_ent2, e->work.d_bucket, e->index_bits, e->n_index);
 }
 
 // Shared searches with DUST: the reverse pass's index. A reverse search whose
@@ -931,26 +929,26 @@ static int build_index(rc_engine *e)
 static int build_masked_index(rc_engine *e)
 {
     const uint32_t n = e->tile_ntx;
-    CHK(e->d_tile_masked.ensure(std::max<uint32_t>(n, 1)));
-    launch_tx_masked(e->d_tile_tx.p, n, e->d_dmask.p + 1, e->d_tile_masked.p, e->st);
+    CHK(e->work.d_tile_masked.ensure(std::max<uint32_t>(n, 1)));
+    launch_tx_masked(e->work.d_tile_tx.p, n, e->work.d_dmask.p + 1, e->work.d_tile_masked.p, e->st);
     HIPCHK(hipGetLastError());
-    CHK(e->d_rctr.ensure(4));
-    if (!e->mnear_cap) e->mnear_cap = e->tile_total / 32 + (1u << 20);
+    CHK(e->work.d_rctr.ensure(4));
+    if (!e->work.mnear_cap) e->work.mnear_cap = e->tile_total / 32 + (1u << 20);
     unsigned long long cnt = 0;
     for (;;) {
-        CHK(e->d_ment.ensure(e->mnear_cap));
-        CHK(e->d_ment2.ensure(e->mnear_cap));
-        HIPCHK(hipMemsetAsync(e->d_rctr.p, 0, sizeof(unsigned long long), e->st));
-        launch_near_fill(e->has_amb, e->d_tile_tx.p, n, e->d_tile_masked.p, e->d_F.p + FRONT_PAD,
-                         e->has_amb ? e->d_AF.p + FRONT_PAD : nullptr, e->d_dmask.p + 1, e->d_ment.p, e->mnear_cap,
-                         e->d_rctr.p, e->o.word_size, e->st);
+        CHK(e->work.d_ment.ensure(e->work.mnear_cap));
+        CHK(e->work.d_ment2.ensure(e->work.mnear_cap));
+        HIPCHK(hipMemsetAsync(e->work.d_rctr.p, 0, sizeof(unsigned long long), e->st));
+        launch_near_fill(e->has_amb, e->work.d_tile_tx.p, n, e->work.d_tile_masked.p, e->work.d_F.p + FRONT_PAD,
+                         e->has_amb ? e->work.d_AF.p + FRONT_PAD : nullptr, e->work.d_dmask.p + 1, e->work.d_ment.p,
+                         e->work.mnear_cap, e->work.d_rctr.p, e->o.word_size, e->st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&cnt, e->d_rctr.p, sizeof cnt, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&cnt, e->work.d_rctr.p, sizeof cnt, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
-        if (cnt <= e->mnear_cap) break;
-        e->mnear_cap = cnt + cnt / 4 + (1u << 20);
+        if (cnt <= e->work.mnear_cap) break;
+        e->work.mnear_cap = cnt + cnt / 4 + (1u << 20);
     }
-    CHK(sort_index(e, e->d_ment, e->d_ment2, cnt, 0u, 2, e->d_mbucket, e->mindex_bits));
+    CHK(sort_index(e, e->work.d_ment, e->work.d_ment2, cnt, 0u, 2, e->work.d_mbucket, e->mindex_bits));
     e->n_mindex = cnt;
     e->tm.near_index += (double)cnt;
     return RC_OK;
@@ -972,10 +970,10 @@ static uint32_t iso_genes(const rc_engine *e, uint32_t g0, uint32_t g1, std::vec
 static Db make_db(rc_engine *e)
 {
     Db db;
-    db.F = e->d_F.p + FRONT_PAD;
-    db.RC = e->d_RC.p + FRONT_PAD;
-    db.AF = e->has_amb ? e->d_AF.p + FRONT_PAD : nullptr;
-    db.ARC = e->has_amb ? e->d_ARC.p + FRONT_PAD : nullptr;
+    db.F = e->work.d_F.p + FRONT_PAD;
+    db.RC = e->work.d_RC.p + FRONT_PAD;
+    db.AF = e->has_amb ? e->work.d_AF.p + FRONT_PAD : nullptr;
+    db.ARC = e->has_amb ? e->work.d_ARC.p + FRONT_PAD : nullptr;
     db.total = e->tile_total;
     db.tx = e->d_tx.p;
     db.tx_gene = e->d_tx_gene.p;
@@ -985,9 +983,9 @@ static Db make_db(rc_engine *e)
     db.gene_sample = e->d_gene_sample.p;
     db.sample_gene_begin = e->d_sample_gene_begin.p;
     db.sample_tx_begin = e->d_sample_tx_begin.p;
-    db.sample_pos_begin = e->d_sample_pos.p;
-    db.txstart = e->d_txstart.p + 1;
-    db.dmask = e->o.dust_level > 0 ? e->d_dmask.p + 1 : nullptr;
+    db.sample_pos_begin = e->work.d_sample_pos.p;
+    db.txstart = e->work.d_txstart.p + 1;
+    db.dmask = e->o.dust_level > 0 ? e->work.d_dmask.p + 1 : nullptr;
     db.n_samples = (int32_t)e->samples.size();
     return db;
 }
@@ -1077,24 +1075,24 @@ static int reverse_pass(rc_engine *e, int ti, const Db &db, const Index &ixm, ui
     }
     std::vector<int32_t> rrange;
     mask_ranges(rmask, N, rrange);
-    CHK(e->d_rtmask.ensure(rmask.size()));
-    CHK(e->d_rtrange.ensure(rrange.size()));
-    HIPCHK(hipMemcpyAsync(e->d_rtmask.p, rmask.data(), rmask.size() * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemcpyAsync(e->d_rtrange.p, rrange.data(), rrange.size() * 4, hipMemcpyHostToDevice, e->st));
+    CHK(e->work.d_rtmask.ensure(rmask.size()));
+    CHK(e->work.d_rtrange.ensure(rrange.size()));
+    HIPCHK(hipMemcpyAsync(e->work.d_rtmask.p, rmask.data(), rmask.size() * 8, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemcpyAsync(e->work.d_rtrange.p, rrange.data(), rrange.size() * 4, hipMemcpyHostToDevice, e->st));
     std::vector<uint32_t> ilist, ioff(1, 0);
     for (auto &r : runs) ioff.push_back(ioff.back() + iso_genes(e, e->sample_gene_begin[r.first],
                                                                  e->sample_gene_begin[r.second], ilist));
     CHK(e->d_iso_list_r.ensure(std::max<size_t>(ilist.size(), 1)));
     if (!ilist.empty())
         HIPCHK(hipMemcpyAsync(e->d_iso_list_r.p, ilist.data(), ilist.size() * 4, hipMemcpyHostToDevice, e->st));
-    CHK(e->d_rctr.ensure(4));
-    CHK(e->d_big_out.ensure(std::max<uint64_t>(e->big_list_cap, 1)));
+    CHK(e->work.d_rctr.ensure(4));
+    CHK(e->work.d_big_out.ensure(std::max<uint64_t>(e->big_list_cap, 1)));
     if (!e->rseed_cap) e->rseed_cap = 1u << 20;
     unsigned long long cnt = 0;
     for (;;) {
-        CHK(e->d_rseeds.ensure(e->rseed_cap));
-        CHK(e->d_rseed_gene.ensure(e->rseed_cap));
-        HIPCHK(hipMemsetAsync(e->d_rctr.p + 1, 0, 2 * sizeof(unsigned long long), e->st));
+        CHK(e->work.d_rseeds.ensure(e->rseed_cap));
+        CHK(e->work.d_rseed_gene.ensure(e->rseed_cap));
+        HIPCHK(hipMemsetAsync(e->work.d_rctr.p + 1, 0, 2 * sizeof(unsigned long long), e->st));
         HIPCHK(hipMemsetAsync(e->d_status.p, 0, 4 * sizeof(unsigned int), e->st));
         for (size_t ri = 0; ri < runs.size(); ri++) {
             const auto &r = runs[ri];
@@ -1106,26 +1104,26 @@ static int reverse_pass(rc_engine *e, int ti, const Db &db, const Index &ixm, ui
             S.rev = 1;
             S.tx_pos = e->d_tx_pos.p;
             S.iso_pre_g = e->d_iso_pre.p;
-            S.rseeds = e->d_rseeds.p;
-            S.rseed_gene = e->d_rseed_gene.p;
+            S.rseeds = e->work.d_rseeds.p;
+            S.rseed_gene = e->work.d_rseed_gene.p;
             S.rseed_cap = e->rseed_cap;
-            S.rseed_n = e->d_rctr.p + 1;
+            S.rseed_n = e->work.d_rctr.p + 1;
             S.gene_begin = e->sample_gene_begin[r.first];
             S.gene_end = e->sample_gene_begin[r.second];
-            S.tmask = e->d_rtmask.p;
+            S.tmask = e->work.d_rtmask.p;
             S.tmw = tw;
-            S.trange = e->d_rtrange.p;
+            S.trange = e->work.d_rtrange.p;
             S.xbits = e->xbits;
             S.max_iso = max_iso(e->xbits);
             S.status = e->d_status.p;
-            S.big_out = e->d_big_out.p;   // (never used: the pass keeps no seeds of its own)
-            S.big_n = e->d_rctr.p + 2;
+            S.big_out = e->work.d_big_out.p;   // (never used: the pass keeps no seeds of its own)
+            S.big_n = e->work.d_rctr.p + 2;
             S.big_list_cap = 0;
             launch_seed(e->has_amb, db, ixm, S, e->st);
             HIPCHK(hipGetLastError());
         }
         unsigned int status = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, e->d_rctr.p + 1, sizeof cnt, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&cnt, e->work.d_rctr.p + 1, sizeof cnt, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
         if (status & 2u)
@@ -1138,15 +1136,15 @@ static int reverse_pass(rc_engine *e, int ti, const Db &db, const Index &ixm, ui
     e->n_rseeds += cnt;
     e->tm.reverse_seeds += (double)cnt;
     if (cnt) {
-        CHK(e->d_rs_key.ensure(cnt));
-        CHK(e->d_rs_idx.ensure(cnt));
+        CHK(e->work.d_rs_key.ensure(cnt));
+        CHK(e->work.d_rs_idx.ensure(cnt));
         size_t tmp = 0;
         rocprim::counting_iterator<uint32_t> iota(0u);
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, e->d_rseed_gene.p, e->d_rs_key.p, iota, e->d_rs_idx.p,
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, e->work.d_rseed_gene.p, e->work.d_rs_key.p, iota, e->work.d_rs_idx.p,
                                          (size_t)cnt, 0u, 32u, e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::radix_sort_pairs(e->d_tmp.p, tmp, e->d_rseed_gene.p, e->d_rs_key.p, iota, e->d_rs_idx.p,
-                                         (size_t)cnt, 0u, 32u, e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::radix_sort_pairs(e->work.d_tmp.p, tmp, e->work.d_rseed_gene.p, e->work.d_rs_key.p, iota,
+                                         e->work.d_rs_idx.p, (size_t)cnt, 0u, 32u, e->st));
     }
     return RC_OK;
 }
@@ -1203,27 +1201,27 @@ static int grow_hsp(rc_engine *e, uint64_t n)
 }
 
 // The loaded tile's packed working copy (FRONT_PAD zero words in front, zero
-// words behind); ev[0] marks the start of the packing.
+// words behind); EV_PACK0 marks the start of the packing.
 static int pack_tile(rc_engine *e)
 {
     const uint64_t total = e->tile_total;
     const uint64_t nwords = (total + 31) / 32 + 2;
-    CHK(e->d_F.ensure(nwords + 4 + FRONT_PAD));
-    CHK(e->d_RC.ensure(nwords + 4 + FRONT_PAD));
-    HIPCHK(hipMemsetAsync(e->d_F.p, 0, FRONT_PAD * 8, e->st));
-    HIPCHK(hipMemsetAsync(e->d_RC.p, 0, FRONT_PAD * 8, e->st));
-    HIPCHK(hipMemsetAsync(e->d_F.p + FRONT_PAD + nwords, 0, 4 * 8, e->st));
-    HIPCHK(hipMemsetAsync(e->d_RC.p + FRONT_PAD + nwords, 0, 4 * 8, e->st));
+    CHK(e->work.d_F.ensure(nwords + 4 + FRONT_PAD));
+    CHK(e->work.d_RC.ensure(nwords + 4 + FRONT_PAD));
+    HIPCHK(hipMemsetAsync(e->work.d_F.p, 0, FRONT_PAD * 8, e->st));
+    HIPCHK(hipMemsetAsync(e->work.d_RC.p, 0, FRONT_PAD * 8, e->st));
+    HIPCHK(hipMemsetAsync(e->work.d_F.p + FRONT_PAD + nwords, 0, 4 * 8, e->st));
+    HIPCHK(hipMemsetAsync(e->work.d_RC.p + FRONT_PAD + nwords, 0, 4 * 8, e->st));
     if (e->has_amb) {
-        CHK(e->d_AF.ensure(nwords + 4 + FRONT_PAD));
-        CHK(e->d_ARC.ensure(nwords + 4 + FRONT_PAD));
-        HIPCHK(hipMemsetAsync(e->d_AF.p, 0, (nwords + 4 + FRONT_PAD) * 8, e->st));
-        HIPCHK(hipMemsetAsync(e->d_ARC.p, 0, (nwords + 4 + FRONT_PAD) * 8, e->st));
+        CHK(e->work.d_AF.ensure(nwords + 4 + FRONT_PAD));
+        CHK(e->work.d_ARC.ensure(nwords + 4 + FRONT_PAD));
+        HIPCHK(hipMemsetAsync(e->work.d_AF.p, 0, (nwords + 4 + FRONT_PAD) * 8, e->st));
+        HIPCHK(hipMemsetAsync(e->work.d_ARC.p, 0, (nwords + 4 + FRONT_PAD) * 8, e->st));
     }
-    HIPCHK(hipEventRecord(e->ev[0], e->st));
-    launch_pack(e->tile_direct ? e->d_ascii.p : e->d_tile_ascii.p, total, nwords, e->d_F.p + FRONT_PAD,
-                e->d_RC.p + FRONT_PAD, e->has_amb ? e->d_AF.p + FRONT_PAD : nullptr,
-                e->has_amb ? e->d_ARC.p + FRONT_PAD : nullptr, e->st);
+    HIPCHK(hipEventRecord(e->ev[EV_PACK0], e->st));
+    launch_pack(e->tile_direct ? e->d_ascii.p : e->work.d_tile_ascii.p, total, nwords, e->work.d_F.p + FRONT_PAD,
+                e->work.d_RC.p + FRONT_PAD, e->has_amb ? e->work.d_AF.p + FRONT_PAD : nullptr,
+                e->has_amb ? e->work.d_ARC.p + FRONT_PAD : nullptr, e->st);
     HIPCHK(hipGetLastError());
     return RC_OK;
 }
@@ -1234,16 +1232,16 @@ static int pack_tile(rc_engine *e)
 static int dust_samples(rc_engine *e, const std::vector<int> &ss, hipStream_t st)
 {
     const uint32_t dblocks = 256 * 28;   // at least the resident waves of the chunk kernel (<= 7 per SIMD): their scratch
-    CHK(e->d_dust_scratch.ensure(dust_scratch_words(dblocks)));
-    CHK(e->d_dust_events.ensure(dust_event_words(dblocks)));
+    CHK(e->work.d_dust_scratch.ensure(dust_scratch_words(dblocks)));
+    CHK(e->work.d_dust_events.ensure(dust_event_words(dblocks)));
     int f = -1, l = -1;
     auto flush = [&]() {
         if (f >= 0) {
             const uint32_t tx0 = e->tile_tx_first[f];
             launch_dust(e->has_amb, e->tile_pos[f], e->tile_pos[l] + align_up(e->samples[l].nbases),
-                        e->d_F.p + FRONT_PAD, e->has_amb ? e->d_AF.p + FRONT_PAD : nullptr, e->d_txstart.p + 1,
-                        e->d_tile_tx.p + tx0, e->tile_tx_first[l + 1] - tx0, e->o.dust_level, e->o.dust_window,
-                        e->o.dust_linker, e->d_dust_scratch.p, e->d_dust_events.p, dblocks, e->d_dmask.p + 1,
+                        e->work.d_F.p + FRONT_PAD, e->has_amb ? e->work.d_AF.p + FRONT_PAD : nullptr, e->work.d_txstart.p + 1,
+                        e->work.d_tile_tx.p + tx0, e->tile_tx_first[l + 1] - tx0, e->o.dust_level, e->o.dust_window,
+                        e->o.dust_linker, e->work.d_dust_scratch.p, e->work.d_dust_events.p, dblocks, e->work.d_dmask.p + 1,
                         st);
         }
         f = l = -1;
@@ -1280,7 +1278,7 @@ struct TileCtx {
 
 // Stage 1: the tile's tables and packed copy, DUST masks (on the second
 // stream), the seed index (built, or the previous tile's) and, for shared
-// searches with DUST, the near-mask index. Events ev[0] .. ev[2].
+// searches with DUST, the near-mask index. Events EV_PACK0, EV_INDEX0, EV_ALIGN0.
 static int index_stage(rc_engine *e, int ti)
 {
     {
@@ -1298,8 +1296,8 @@ static int index_stage(rc_engine *e, int ti)
     // at a time -- RC_SHARE=0, not spec 5b -- it holds the a part's samples
     // too, and they differ from tile to tile)
     const bool b_only_index = e->share || e->o.symmetric;
-    const bool reuse = b_only_index && TT.bchunk >= 0 && TT.bchunk == e->idx_bchunk && TT.bstart == e->idx_bstart &&
-                       e->d_dmask.cap >= (total >> 6) + 4;
+    const bool reuse = b_only_index && TT.bchunk >= 0 && TT.bchunk == e->work.idx_bchunk && TT.bstart == e->work.idx_bstart &&
+                       e->work.d_dmask.cap >= (total >> 6) + 4;
     const uint64_t dtot = reuse ? TT.bstart : total;   // masks cleared: the a part only when reusing
     // the samples whose masks DUST computes here, in tile order: a split
     // tile's a part and (unless its masks are kept) its b part, all samples
@@ -1309,43 +1307,43 @@ static int index_stage(rc_engine *e, int ti)
     e->dmask_only.clear();   // every sample of this tile gets its mask
     if (dust) {
         const size_t mw = (total >> 6) + 4;
-        CHK(e->d_dmask.ensure(mw));
-        HIPCHK(hipMemsetAsync(e->d_dmask.p, 0, (reuse ? 1 + (dtot >> 6) : mw) * 8, e->st));
+        CHK(e->work.d_dmask.ensure(mw));
+        HIPCHK(hipMemsetAsync(e->work.d_dmask.p, 0, (reuse ? 1 + (dtot >> 6) : mw) * 8, e->st));
         for (int s : TT.samples) {
             if (reuse && e->tile_pos[s] >= TT.bstart) continue;
             const uint64_t io = s < (int)e->dust_imp_off.size() ? e->dust_imp_off[s] : ~0ull;
             if (io == ~0ull) {
                 dust_here.push_back(s);
             } else if (e->samples[s].nbases) {
-                HIPCHK(hipMemcpyAsync(e->d_dmask.p + 1 + (e->tile_pos[s] >> 6), e->d_dust_imp.p + io,
+                HIPCHK(hipMemcpyAsync(e->work.d_dmask.p + 1 + (e->tile_pos[s] >> 6), e->d_dust_imp.p + io,
                                       ((e->samples[s].nbases + 63) >> 6) * 8, hipMemcpyDeviceToDevice, e->st));
             }
         }
     }
-    HIPCHK(hipEventRecord(e->ev[1], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_INDEX0], e->st));
     // DUST masks of the tile's transcripts (the query side), bit per base, on
     // the second stream: a compute-bound scan beside the HBM-bound index
     // build, started with the fill (r03, hand-written sort and DUST: index
     // phase 55.7 vs 58.1 ms at C3 when started after the sort's table kernels)
     if (dust) {
-        HIPCHK(hipEventRecord(e->evd[2], e->st));
-        HIPCHK(hipStreamWaitEvent(e->st2, e->evd[2], 0));
-        HIPCHK(hipEventRecord(e->evd[0], e->st2));
+        HIPCHK(hipEventRecord(e->evd[EVD_READY], e->st));
+        HIPCHK(hipStreamWaitEvent(e->st2, e->evd[EVD_READY], 0));
+        HIPCHK(hipEventRecord(e->evd[EVD_DUST0], e->st2));
         CHK(dust_samples(e, dust_here, e->st2));
-        HIPCHK(hipEventRecord(e->evd[1], e->st2));
+        HIPCHK(hipEventRecord(e->evd[EVD_DUST1], e->st2));
     }
     if (reuse)
         e->tm.index_reused += 1.0;
     else
         CHK(build_index(e));
-    e->idx_bchunk = TT.bchunk;
-    e->idx_bstart = TT.bstart;
+    e->work.idx_bchunk = TT.bchunk;
+    e->work.idx_bstart = TT.bstart;
     HIPCHK(hipGetLastError());
-    if (dust) HIPCHK(hipStreamWaitEvent(e->st, e->evd[1], 0));
+    if (dust) HIPCHK(hipStreamWaitEvent(e->st, e->evd[EVD_DUST1], 0));
     // shared searches with DUST: reverse-search runs with no usable word of
     // the forward query inside come from a reverse pass over a near-mask index
     if (e->share && dust) CHK(build_masked_index(e));
-    HIPCHK(hipEventRecord(e->ev[2], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_ALIGN0], e->st));
     return RC_OK;
 }
 
@@ -1362,10 +1360,10 @@ static int plan_stage(rc_engine *e, TileCtx &C)
     const int tw = C.tw = mask_words(N);
     std::vector<int32_t> trange;
     mask_ranges(tmask, N, trange);
-    CHK(e->d_tmask.ensure(tmask.size()));
-    CHK(e->d_trange.ensure(trange.size()));
-    HIPCHK(hipMemcpyAsync(e->d_tmask.p, tmask.data(), tmask.size() * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemcpyAsync(e->d_trange.p, trange.data(), trange.size() * 4, hipMemcpyHostToDevice, e->st));
+    CHK(e->work.d_tmask.ensure(tmask.size()));
+    CHK(e->work.d_trange.ensure(trange.size()));
+    HIPCHK(hipMemcpyAsync(e->work.d_tmask.p, tmask.data(), tmask.size() * 8, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemcpyAsync(e->work.d_trange.p, trange.data(), trange.size() * 4, hipMemcpyHostToDevice, e->st));
     std::vector<uint32_t> ilist;
     C.rg0.assign(R, 0);
     C.rg1.assign(R, 0);
@@ -1382,10 +1380,10 @@ static int plan_stage(rc_engine *e, TileCtx &C)
     CHK(e->d_iso_list.ensure(std::max<size_t>(ilist.size(), 1)));
     if (!ilist.empty())
         HIPCHK(hipMemcpyAsync(e->d_iso_list.p, ilist.data(), ilist.size() * 4, hipMemcpyHostToDevice, e->st));
-    CHK(e->d_gc_off.ensure(std::max<size_t>(C.gcb[R], 1)));
-    CHK(e->d_gc_cnt.ensure(std::max<size_t>(C.gcb[R], 1)));
-    CHK(e->d_gcount.ensure(std::max<size_t>(C.cnb[R], 1)));
-    CHK(e->d_gscan.ensure(std::max<size_t>(C.cnb[R], 1)));
+    CHK(e->work.d_gc_off.ensure(std::max<size_t>(C.gcb[R], 1)));
+    CHK(e->work.d_gc_cnt.ensure(std::max<size_t>(C.gcb[R], 1)));
+    CHK(e->work.d_gcount.ensure(std::max<size_t>(C.cnb[R], 1)));
+    CHK(e->work.d_gscan.ensure(std::max<size_t>(C.cnb[R], 1)));
     CHK(e->d_shard_cnt.ensure(2 * NSHARD));
     CHK(e->d_shard_prefix.ensure(NSHARD + 1));
     {
@@ -1404,13 +1402,13 @@ static int plan_stage(rc_engine *e, TileCtx &C)
         e->ovf_cap = std::max<uint64_t>(e->ovf_cap, oc ? (uint64_t)oc : nb / 4 + 1024);
     }
     C.db = make_db(e);
-    C.ix.ent = e->d_ent2.p;
-    C.ix.bucket = e->d_bucket.p;
-    C.ix.pos_tx = e->d_pos_tx.p;
+    C.ix.ent = e->work.d_ent2.p;
+    C.ix.bucket = e->work.d_bucket.p;
+    C.ix.pos_tx = e->work.d_pos_tx.p;
     C.ix.bits = e->index_bits;
     C.ixm = C.ix;
-    C.ixm.ent = e->d_ment2.p;
-    C.ixm.bucket = e->d_mbucket.p;
+    C.ixm.ent = e->work.d_ment2.p;
+    C.ixm.bucket = e->work.d_mbucket.p;
     C.ixm.bits = e->mindex_bits;
     CHK(e->d_count.ensure(DC_N));
     return RC_OK;
@@ -1424,28 +1422,28 @@ static int seed_big_passes(rc_engine *e, const TileCtx &C, const SeedParams &S, 
 {
     const uint64_t BIG_CHUNK = 2048;
     unsigned long long *const big_retry_n = e->d_count.p + DC_BIG_RETRY;
-    uint64_t *list = e->d_big_out.p;
+    uint64_t *list = e->work.d_big_out.p;
     while (!again && nb) {
         if ((uint64_t)e->big_cap > (1ull << 22))
             return fail(RC_E_LIMIT, "a (query gene, subject sample) pass has more than 2^22 seeds");
         const uint64_t chunk = std::min<uint64_t>(nb, BIG_CHUNK);
-        CHK(e->d_big_list.ensure(nb));
-        CHK(e->d_big_retry.ensure(nb));
-        CHK(e->d_big_seeds.ensure(chunk * e->big_cap));
-        CHK(e->d_big_seg.ensure(chunk * (e->big_cap + 1)));
-        CHK(e->d_big_segT.ensure(chunk * e->big_cap));
-        if (list != e->d_big_list.p)
-            HIPCHK(hipMemcpyAsync(e->d_big_list.p, list, nb * 8, hipMemcpyDeviceToDevice, e->st));
+        CHK(e->work.d_big_list.ensure(nb));
+        CHK(e->work.d_big_retry.ensure(nb));
+        CHK(e->work.d_big_seeds.ensure(chunk * e->big_cap));
+        CHK(e->work.d_big_seg.ensure(chunk * (e->big_cap + 1)));
+        CHK(e->work.d_big_segT.ensure(chunk * e->big_cap));
+        if (list != e->work.d_big_list.p)
+            HIPCHK(hipMemcpyAsync(e->work.d_big_list.p, list, nb * 8, hipMemcpyDeviceToDevice, e->st));
         HIPCHK(hipMemsetAsync(big_retry_n, 0, sizeof(unsigned long long), e->st));
         SeedParams B = S;
-        B.big_retry = e->d_big_retry.p;
+        B.big_retry = e->work.d_big_retry.p;
         B.big_list_cap = nb;
         B.big_cap = e->big_cap;
-        B.big_seeds = e->d_big_seeds.p;
-        B.big_seg = e->d_big_seg.p;
-        B.big_segT = e->d_big_segT.p;
+        B.big_seeds = e->work.d_big_seeds.p;
+        B.big_seg = e->work.d_big_seg.p;
+        B.big_segT = e->work.d_big_segT.p;
         for (uint64_t c0 = 0; c0 < nb; c0 += chunk) {
-            B.big_list = e->d_big_list.p + c0;
+            B.big_list = e->work.d_big_list.p + c0;
             launch_seed_big(e->has_amb, C.db, C.ix, B, (uint32_t)std::min<uint64_t>(chunk, nb - c0), e->st);
             HIPCHK(hipGetLastError());
         }
@@ -1459,9 +1457,8 @@ static int seed_big_passes(rc_engine *e, const TileCtx &C, const SeedParams &S, 
         again = (status & 1u) != 0;
         nb = nr;
         // the retry entries become the next list (buffers swapped, not copied)
-        std::swap(e->d_big_list.p, e->d_big_retry.p);
-        std::swap(e->d_big_list.cap, e->d_big_retry.cap);
-        list = e->d_big_list.p;
+        e->work.d_big_list.swap(e->work.d_big_retry);
+        list = e->work.d_big_list.p;
         if (nb) e->big_cap *= 2;
     }
     return RC_OK;
@@ -1469,29 +1466,29 @@ static int seed_big_passes(rc_engine *e, const TileCtx &C, const SeedParams &S, 
 
 // Stage 3: seeds and candidates of every run (the reverse pass first, for
 // shared searches with DUST), again with larger buffers while one overflows;
-// then the candidates' shard prefix. Events ev[3], ev[9].
+// then the candidates' shard prefix. Events EV_SEED0, EV_SEED1.
 static int seed_stage(rc_engine *e, TileCtx &C)
 {
     const size_t R = C.runs.size();
     std::vector<unsigned long long> shard_cnt(2 * NSHARD);
     unsigned long long *const big_n = e->d_count.p + DC_BIG;
     uint64_t n_big = 0;
-    HIPCHK(hipEventRecord(e->ev[3], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_SEED0], e->st));
     if (e->share && e->o.dust_level > 0 && e->n_mindex) CHK(reverse_pass(e, C.ti, C.db, C.ixm, C.n_rs));
     for (int attempt = 0;; attempt++) {
         if (attempt == 6) return fail(RC_E_NOMEM, "seed/candidate buffers kept overflowing");
         if (e->seed_cap * NSHARD > 0xFFFFFFFFull || e->cand_cap * NSHARD > 0xFFFFFFFFull)
             return fail(RC_E_LIMIT, "more than 2^32 seeds or candidates in a tile: use more shards or smaller tiles");
-        CHK(e->d_seeds.ensure(e->seed_cap * NSHARD));
-        CHK(e->d_cands.ensure(e->cand_cap * NSHARD));
-        if (e->share) CHK(e->d_list2.ensure(e->cand_cap * NSHARD));
+        CHK(e->work.d_seeds.ensure(e->seed_cap * NSHARD));
+        CHK(e->work.d_cands.ensure(e->cand_cap * NSHARD));
+        if (e->share) CHK(e->work.d_list2.ensure(e->cand_cap * NSHARD));
         HIPCHK(hipMemsetAsync(e->d_count.p + DC_LIST2, 0, sizeof(unsigned long long), e->st));
-        CHK(e->d_big_out.ensure(e->big_list_cap));
+        CHK(e->work.d_big_out.ensure(e->big_list_cap));
         HIPCHK(hipMemsetAsync(e->d_shard_cnt.p, 0, 2 * NSHARD * sizeof(unsigned long long), e->st));
         HIPCHK(hipMemsetAsync(e->d_status.p, 0, 4 * sizeof(unsigned int), e->st));
-        if (C.gcb[R]) HIPCHK(hipMemsetAsync(e->d_gc_cnt.p, 0, C.gcb[R] * 4, e->st));
-        CHK(e->d_prof.ensure(10));
-        HIPCHK(hipMemsetAsync(e->d_prof.p, 0, 10 * sizeof(unsigned long long), e->st));
+        if (C.gcb[R]) HIPCHK(hipMemsetAsync(e->work.d_gc_cnt.p, 0, C.gcb[R] * 4, e->st));
+        CHK(e->work.d_prof.ensure(10));
+        HIPCHK(hipMemsetAsync(e->work.d_prof.p, 0, 10 * sizeof(unsigned long long), e->st));
         // what every run of this attempt shares
         SeedParams S0{};
         S0.word = e->o.word_size;
@@ -1500,29 +1497,29 @@ static int seed_stage(rc_engine *e, TileCtx &C)
         S0.share = e->share ? 1 : 0;
         S0.tx_pos = e->d_tx_pos.p;
         S0.iso_pre_g = e->d_iso_pre.p;
-        S0.rs_rec = e->d_rseeds.p;
-        S0.rs_key = e->d_rs_key.p;
-        S0.rs_idx = e->d_rs_idx.p;
+        S0.rs_rec = e->work.d_rseeds.p;
+        S0.rs_key = e->work.d_rs_key.p;
+        S0.rs_idx = e->work.d_rs_idx.p;
         S0.rs_n = C.n_rs;
-        S0.list2 = e->d_list2.p;
+        S0.list2 = e->work.d_list2.p;
         S0.list2_n = e->d_count.p + DC_LIST2;
-        S0.seeds = e->d_seeds.p;
+        S0.seeds = e->work.d_seeds.p;
         S0.seed_cap = e->seed_cap;
         S0.seed_count = e->d_shard_cnt.p;
-        S0.cands = e->d_cands.p;
+        S0.cands = e->work.d_cands.p;
         S0.cand_cap = e->cand_cap;
         S0.cand_count = e->d_shard_cnt.p + NSHARD;
-        S0.tmask = e->d_tmask.p;
+        S0.tmask = e->work.d_tmask.p;
         S0.tmw = C.tw;
-        S0.trange = e->d_trange.p;
+        S0.trange = e->work.d_trange.p;
         S0.xbits = e->xbits;
         S0.max_iso = max_iso(e->xbits);
         S0.status = e->d_status.p;
-        S0.big_out = e->d_big_out.p;
+        S0.big_out = e->work.d_big_out.p;
         S0.big_n = big_n;
         S0.big_retry_n = e->d_count.p + DC_BIG_RETRY;
         S0.big_list_cap = e->big_list_cap;
-        S0.prof = e->d_prof.p;
+        S0.prof = e->work.d_prof.p;
         bool again = false;
         n_big = 0;
         for (size_t r = 0; r < R && !again; r++) {
@@ -1532,14 +1529,14 @@ static int seed_stage(rc_engine *e, TileCtx &C)
             S.gene_begin = C.rg0[r];
             S.gene_end = C.rg1[r];
             if (C.n_rs) {
-                CHK(e->d_rs_range.ensure((size_t)2 * (C.rg1[r] - C.rg0[r]) + 2));
-                launch_rs_range(e->d_rs_key.p, C.n_rs, C.rg0[r], C.rg1[r], e->d_rs_range.p, e->st);
-                S.rs_range = e->d_rs_range.p;
+                CHK(e->work.d_rs_range.ensure((size_t)2 * (C.rg1[r] - C.rg0[r]) + 2));
+                launch_rs_range(e->work.d_rs_key.p, C.n_rs, C.rg0[r], C.rg1[r], e->work.d_rs_range.p, e->st);
+                S.rs_range = e->work.d_rs_range.p;
             }
             S.iso_list = e->d_iso_list.p + C.ioff[r];
             S.iso_n = C.ioff[r + 1] - C.ioff[r];
-            S.gc_off = e->d_gc_off.p + C.gcb[r];
-            S.gc_cnt = e->d_gc_cnt.p + C.gcb[r];
+            S.gc_off = e->work.d_gc_off.p + C.gcb[r];
+            S.gc_cnt = e->work.d_gc_cnt.p + C.gcb[r];
             launch_seed(e->has_amb, C.db, C.ix, S, e->st);
             HIPCHK(hipGetLastError());
             unsigned int status = 0;
@@ -1560,7 +1557,7 @@ static int seed_stage(rc_engine *e, TileCtx &C)
             n_big += nb;
             CHK(seed_big_passes(e, C, S, nb, again));
         }
-        HIPCHK(hipEventRecord(e->ev[9], e->st));
+        HIPCHK(hipEventRecord(e->ev[EV_SEED1], e->st));
         HIPCHK(hipMemcpyAsync(shard_cnt.data(), e->d_shard_cnt.p, 2 * NSHARD * 8, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
         if (!again) break;
@@ -1592,15 +1589,15 @@ static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
     X.max_len = e->max_len;
     X.thr = e->d_thr.p;
     X.bits10 = e->d_bits10.p;
-    X.cands = e->d_cands.p;
-    X.seeds = e->d_seeds.p;
+    X.cands = e->work.d_cands.p;
+    X.seeds = e->work.d_seeds.p;
     X.shard_prefix = e->d_shard_prefix.p;
     X.n_cand = C.n_cand;
     X.cand_cap = e->cand_cap;
-    X.cand_hsp = e->d_cand_hsp.p;
-    X.cand_nh = e->d_cand_nh.p;
-    X.cand_ovf = e->d_cand_ovf.p;
-    X.ovf = e->d_ovf.p;
+    X.cand_hsp = e->work.d_cand_hsp.p;
+    X.cand_nh = e->work.d_cand_nh.p;
+    X.cand_ovf = e->work.d_cand_ovf.p;
+    X.ovf = e->work.d_ovf.p;
     X.ovf_cap = e->ovf_cap;
     X.ovf_count = cnt + DC_OVF;
     X.status = e->d_status.p;
@@ -1616,24 +1613,24 @@ static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
         X.win = forced ? 1 : (need > smax ? 1 : 0);
         X.dsw = forced ? std::min(forced, smax) : std::min(need, smax);
     }
-    X.defer = e->d_defer.p;
+    X.defer = e->work.d_defer.p;
     X.defer_count = cnt + DC_DEFER;
     X.work = cnt + DC_WORK;
-    X.cand_box = e->d_cand_box.p;
+    X.cand_box = e->work.d_cand_box.p;
     X.share = e->share ? 1 : 0;
     X.which = 0;
     X.dir = 0;
-    X.cand_box2 = e->d_cand_box2.p;
-    X.cand_hsp_r = e->d_cand_hsp_r.p;
-    X.cand_nh_r = e->d_cand_nh_r.p;
-    X.cand_ovf_r = e->d_cand_ovf_r.p;
-    X.defer_r = e->d_defer_r.p;
+    X.cand_box2 = e->work.d_cand_box2.p;
+    X.cand_hsp_r = e->work.d_cand_hsp_r.p;
+    X.cand_nh_r = e->work.d_cand_nh_r.p;
+    X.cand_ovf_r = e->work.d_cand_ovf_r.p;
+    X.defer_r = e->work.d_defer_r.p;
     X.defer_r_count = cnt + DC_DEFER_R;
-    X.list2 = e->d_list2.p;
+    X.list2 = e->work.d_list2.p;
     X.list2_n = cnt + DC_LIST2;
     X.work3 = cnt + DC_WORK3;
-    X.wide0 = e->share ? e->d_wide0.p : nullptr;
-    X.wide1 = e->d_wide1.p;
+    X.wide0 = e->share ? e->work.d_wide0.p : nullptr;
+    X.wide1 = e->work.d_wide1.p;
     X.wide0_n = cnt + DC_WIDE0;
     X.wide1_n = cnt + DC_WIDE1;
     {
@@ -1641,8 +1638,8 @@ static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
         // run had many (C3v: 39 %, C3: 0.002 %): the saving kernel costs
         // the plain one 7 % (RC_RESUME=1 always, 0 never)
         const bool on = e->knobs.resume != -1 ? e->knobs.resume == 1 : e->ovf_frac > 0.02;
-        X.resume = e->res_cap && on ? e->d_resume.p : nullptr;
-        X.res_cap = e->res_cap;
+        X.resume = e->work.res_cap && on ? e->work.d_resume.p : nullptr;
+        X.res_cap = e->work.res_cap;
     }
     X.work_w0 = cnt + DC_WORK_W0;
     X.work_w1 = cnt + DC_WORK_W1;
@@ -1657,37 +1654,37 @@ static ExtParams ext_params(const rc_engine *e, const TileCtx &C)
 static int later_rounds(rc_engine *e, TileCtx &C, const ExtParams &X, uint64_t dn0, uint64_t dn1)
 {
     const uint64_t nsrch = dn0 + dn1, n = std::min(nsrch, e->knobs.later_cap);
-    CHK(e->d_later.ensure(n * LATER_REC));
-    CHK(e->d_lbox0.ensure(n * BOX_REC));
-    CHK(e->d_lbox1.ensure(n * BOX_REC));
-    CHK(e->d_lvc0.ensure(n));
-    CHK(e->d_lvc1.ensure(n));
-    CHK(e->d_llist0.ensure(n));
-    CHK(e->d_llist1.ensure(n));
-    CHK(e->d_lact0.ensure(n));
-    CHK(e->d_lact1.ensure(n));
-    CHK(e->d_lfull0.ensure(std::max<uint64_t>(dn0, 1)));
-    CHK(e->d_lfull1.ensure(std::max<uint64_t>(dn1, 1)));
+    CHK(e->work.d_later.ensure(n * LATER_REC));
+    CHK(e->work.d_lbox0.ensure(n * BOX_REC));
+    CHK(e->work.d_lbox1.ensure(n * BOX_REC));
+    CHK(e->work.d_lvc0.ensure(n));
+    CHK(e->work.d_lvc1.ensure(n));
+    CHK(e->work.d_llist0.ensure(n));
+    CHK(e->work.d_llist1.ensure(n));
+    CHK(e->work.d_lact0.ensure(n));
+    CHK(e->work.d_lact1.ensure(n));
+    CHK(e->work.d_lfull0.ensure(std::max<uint64_t>(dn0, 1)));
+    CHK(e->work.d_lfull1.ensure(std::max<uint64_t>(dn1, 1)));
     const size_t nc = (size_t)MAX_HSP * LATER_CNT + LC_N;
-    CHK(e->d_lcnt.ensure(nc));
-    HIPCHK(hipMemsetAsync(e->d_lcnt.p, 0, nc * sizeof(unsigned long long), e->st));
+    CHK(e->work.d_lcnt.ensure(nc));
+    HIPCHK(hipMemsetAsync(e->work.d_lcnt.p, 0, nc * sizeof(unsigned long long), e->st));
     LaterParams &lat = C.lat;
     lat = LaterParams{};
-    lat.state = e->d_later.p;
+    lat.state = e->work.d_later.p;
     lat.n_search = nsrch;
     lat.n0 = dn0;
     lat.n_cap = n;
     lat.defer0 = X.defer;
     lat.defer1 = X.defer_r;
-    lat.full0 = e->d_lfull0.p;
-    lat.full1 = e->d_lfull1.p;
-    lat.counters = e->d_lcnt.p + (size_t)MAX_HSP * LATER_CNT;
+    lat.full0 = e->work.d_lfull0.p;
+    lat.full1 = e->work.d_lfull1.p;
+    lat.counters = e->work.d_lcnt.p + (size_t)MAX_HSP * LATER_CNT;
     lat.full_n = lat.counters + LC_FULL_N;
-    Cand *const vc[2] = {e->d_lvc0.p, e->d_lvc1.p};
-    uint32_t *const ls[2] = {e->d_llist0.p, e->d_llist1.p};
-    int32_t *const bx[2] = {e->d_lbox0.p, e->d_lbox1.p};
-    uint32_t *const ac[2] = {e->d_lact0.p, e->d_lact1.p};
-    launch_later_rounds(e->has_amb, C.db, X, e->knobs.later_rows == 32, lat, vc, ls, bx, ac, e->d_lcnt.p, e->st);
+    Cand *const vc[2] = {e->work.d_lvc0.p, e->work.d_lvc1.p};
+    uint32_t *const ls[2] = {e->work.d_llist0.p, e->work.d_llist1.p};
+    int32_t *const bx[2] = {e->work.d_lbox0.p, e->work.d_lbox1.p};
+    uint32_t *const ac[2] = {e->work.d_lact0.p, e->work.d_lact1.p};
+    launch_later_rounds(e->has_amb, C.db, X, e->knobs.later_rows == 32, lat, vc, ls, bx, ac, e->work.d_lcnt.p, e->st);
     HIPCHK(hipGetLastError());
     C.later_on = true;
     return RC_OK;
@@ -1719,7 +1716,7 @@ static int print_row_timing(rc_engine *e, const unsigned long long *ctr)
                     "%.4g of %.4g; 16-lane window slides %.4g\n", (double)r16[0], c(DC_STEPS),
             (double)r16[1], c(DC_CANDS), (double)r16[2]);
     unsigned long long pr[10];
-    HIPCHK(hipMemcpy(pr, e->d_prof.p, sizeof pr, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pr, e->work.d_prof.p, sizeof pr, hipMemcpyDeviceToHost));
     fprintf(stderr, "seed kernel block-cycles: prologue %.4g words: usable %.4g lookup %.4g scan %.4g "
                     "hits %.4g (loads %.4g pretest %.4g full test %.4g) sort %.4g write %.4g\n",
             (double)pr[8], (double)pr[9], (double)pr[0], (double)pr[1], (double)(pr[2] + pr[5] + pr[6] + pr[7]),
@@ -1730,37 +1727,37 @@ static int print_row_timing(rc_engine *e, const unsigned long long *ctr)
 // Stage 4: the candidates' extensions (row kernels over first seeds, the
 // later-seed rounds, extend_kernel over what they leave); extend_kernel runs
 // again with a larger HSP overflow buffer while that overflows. Events
-// ev[10], ev[11].
+// EV_EXTEND0, EV_EXTEND1.
 static int extension_stage(rc_engine *e, TileCtx &C)
 {
     const uint64_t n_cand = C.n_cand, slots = e->cand_cap * NSHARD;
     unsigned long long *const cnt = e->d_count.p;
-    CHK(e->d_cand_hsp.ensure(slots));
-    CHK(e->d_cand_nh.ensure(slots));
-    CHK(e->d_cand_ovf.ensure(slots));
-    CHK(e->d_cand_box.ensure(slots * BOX_REC));
+    CHK(e->work.d_cand_hsp.ensure(slots));
+    CHK(e->work.d_cand_nh.ensure(slots));
+    CHK(e->work.d_cand_ovf.ensure(slots));
+    CHK(e->work.d_cand_box.ensure(slots * BOX_REC));
     if (e->share) {
-        CHK(e->d_cand_box2.ensure(slots * BOX_REC));
-        CHK(e->d_cand_hsp_r.ensure(slots));
-        CHK(e->d_cand_nh_r.ensure(slots));
-        CHK(e->d_cand_ovf_r.ensure(slots));
-        CHK(e->d_defer_r.ensure(std::max<uint64_t>(n_cand, 1)));
-        CHK(e->d_wide0.ensure(std::max<uint64_t>(n_cand, 1)));
-        CHK(e->d_wide1.ensure(std::max<uint64_t>(n_cand, 1)));
+        CHK(e->work.d_cand_box2.ensure(slots * BOX_REC));
+        CHK(e->work.d_cand_hsp_r.ensure(slots));
+        CHK(e->work.d_cand_nh_r.ensure(slots));
+        CHK(e->work.d_cand_ovf_r.ensure(slots));
+        CHK(e->work.d_defer_r.ensure(std::max<uint64_t>(n_cand, 1)));
+        CHK(e->work.d_wide0.ensure(std::max<uint64_t>(n_cand, 1)));
+        CHK(e->work.d_wide1.ensure(std::max<uint64_t>(n_cand, 1)));
         // room to continue the first 12 M overflowing extensions of a pass
         // (3.8 GB); later ones start over in the 64-lane pass
-        e->res_cap = e->knobs.resume == 0 ? 0u : (uint32_t)std::min<uint64_t>(n_cand, 12u << 20);
-        if (e->knobs.resume != 1 && e->ovf_frac <= 0.02) e->res_cap = 0;   // not needed: no buffer
-        if (e->res_cap) CHK(e->d_resume.ensure((size_t)e->res_cap * RES_REC));
+        e->work.res_cap = e->knobs.resume == 0 ? 0u : (uint32_t)std::min<uint64_t>(n_cand, 12u << 20);
+        if (e->knobs.resume != 1 && e->ovf_frac <= 0.02) e->work.res_cap = 0;   // not needed: no buffer
+        if (e->work.res_cap) CHK(e->work.d_resume.ensure((size_t)e->work.res_cap * RES_REC));
     }
-    CHK(e->d_defer.ensure(std::max<uint64_t>(n_cand, 1)));
+    CHK(e->work.d_defer.ensure(std::max<uint64_t>(n_cand, 1)));
     // later-seed rounds: their parameters (C.lat) once they ran (a retry
     // finishes the searches again from the states, and extend_kernel takes the
     // lists of the searches they left whole instead of first_finish_kernel's)
     C.later_on = false;
     for (int attempt = 0;; attempt++) {
         if (attempt == 4) return fail(RC_E_NOMEM, "HSP overflow buffer kept overflowing");
-        CHK(e->d_ovf.ensure(e->ovf_cap));
+        CHK(e->work.d_ovf.ensure(e->ovf_cap));
         if (attempt == 0) {
             // every slot the extension counts in; the seed stage's (DC_BIG,
             // DC_BIG_RETRY, DC_LIST2) and the groups' (DC_MBIG) stand
@@ -1775,7 +1772,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
         HIPCHK(hipMemsetAsync(e->d_status.p, 0, 4 * sizeof(unsigned int), e->st));
         ExtParams X = ext_params(e, C);
         if (attempt == 0) {
-            HIPCHK(hipEventRecord(e->ev[10], e->st));
+            HIPCHK(hipEventRecord(e->ev[EV_EXTEND0], e->st));
             launch_extend_rows(e->has_amb, C.db, X, e->st);
             HIPCHK(hipGetLastError());
             // only the searches the row kernels left (defer lists) can have
@@ -1790,8 +1787,8 @@ static int extension_stage(rc_engine *e, TileCtx &C)
             const uint64_t want = std::min<uint64_t>(2 * nd, (uint64_t)(MAX_HSP - 1) * nd) + 1024;
             if (want > e->ovf_cap && !e->knobs.ovf_cap0) {
                 e->ovf_cap = want;
-                CHK(e->d_ovf.ensure(e->ovf_cap));
-                X.ovf = e->d_ovf.p;
+                CHK(e->work.d_ovf.ensure(e->ovf_cap));
+                X.ovf = e->work.d_ovf.p;
                 X.ovf_cap = e->ovf_cap;
             }
             // (RC_LATER=0: extend_kernel runs the deferred searches whole)
@@ -1812,7 +1809,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
         }
         launch_extend_retry(e->has_amb, C.db, X, e->st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->ev[11], e->st));
+        HIPCHK(hipEventRecord(e->ev[EV_EXTEND1], e->st));
         unsigned long long ovn = 0, ctr[DC_COUNTERS_END - DC_COUNTERS] = {};
         const auto c = [&](int slot) { return (double)ctr[slot - DC_COUNTERS]; };
         unsigned long long nwide[2] = {0, 0};   // shared searches: candidates the 64-lane passes took
@@ -1845,7 +1842,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
             e->tm.defer_outside += (double)why[2];
             if (C.later_on) {   // later-seed rounds: seeds extended on the row kernels, searches run whole
                 std::vector<unsigned long long> lc((size_t)MAX_HSP * LATER_CNT + LC_N);
-                HIPCHK(hipMemcpy(lc.data(), e->d_lcnt.p, lc.size() * sizeof(unsigned long long),
+                HIPCHK(hipMemcpy(lc.data(), e->work.d_lcnt.p, lc.size() * sizeof(unsigned long long),
                                  hipMemcpyDeviceToHost));
                 for (int r = 0; r < MAX_HSP; r++) e->tm.later_seeds += (double)lc[(size_t)r * LATER_CNT];
                 e->tm.later_whole += (double)lc[(size_t)MAX_HSP * LATER_CNT + LC_WHOLE];
@@ -1860,7 +1857,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
 // Stage 6: (query gene, subject sample) -> contiguous HSPs, appended to the
 // shard's store. Direct groups of every run first, in candidate order;
 // mirrored groups (spec 5b: the subject->query direction of the same
-// alignments) follow, each sorted into the order that search emits. Event ev[4].
+// alignments) follow, each sorted into the order that search emits. Event EV_GROUPS1.
 static int group_stage(rc_engine *e, const TileCtx &C)
 {
     const int N = (int)e->samples.size();
@@ -1868,10 +1865,10 @@ static int group_stage(rc_engine *e, const TileCtx &C)
     const auto &cnb = C.cnb;
     GroupParams G{};
     G.N = N;
-    G.cand_nh = e->d_cand_nh.p;
-    G.cand_hsp = e->d_cand_hsp.p;
-    G.cand_ovf = e->d_cand_ovf.p;
-    G.ovf = e->d_ovf.p;
+    G.cand_nh = e->work.d_cand_nh.p;
+    G.cand_hsp = e->work.d_cand_hsp.p;
+    G.cand_ovf = e->work.d_cand_ovf.p;
+    G.ovf = e->work.d_ovf.p;
     G.shard_prefix = e->d_shard_prefix.p;
     G.n_cand = C.n_cand;
     G.cand_cap = e->cand_cap;
@@ -1884,36 +1881,36 @@ static int group_stage(rc_engine *e, const TileCtx &C)
     auto exscan = [&](const uint32_t *in, uint64_t *out, size_t n) -> int {
         size_t tmp = 0;
         HIPCHK(rocprim::exclusive_scan(nullptr, tmp, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::exclusive_scan(e->d_tmp.p, tmp, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->work.d_tmp.p, tmp, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), e->st));
         return RC_OK;
     };
     auto run_group = [&](size_t r) {
         GroupParams g = G;
         g.gene_begin = C.rg0[r];
         g.gene_end = C.rg1[r];
-        g.gc_off = e->d_gc_off.p + C.gcb[r];
-        g.gc_cnt = e->d_gc_cnt.p + C.gcb[r];
-        g.cnt = e->d_gcount.p + cnb[r];
-        g.scan = e->d_gscan.p + cnb[r];
+        g.gc_off = e->work.d_gc_off.p + C.gcb[r];
+        g.gc_cnt = e->work.d_gc_cnt.p + C.gcb[r];
+        g.cnt = e->work.d_gcount.p + cnb[r];
+        g.scan = e->work.d_gscan.p + cnb[r];
         return g;
     };
     std::vector<uint64_t> nd(R, 0);
     for (size_t r = 0; r < R; r++) {
         const size_t nsgrp = cnb[r + 1] - cnb[r] - 1;
-        HIPCHK(hipMemsetAsync(e->d_gcount.p + cnb[r] + nsgrp, 0, 4, e->st));
+        HIPCHK(hipMemsetAsync(e->work.d_gcount.p + cnb[r] + nsgrp, 0, 4, e->st));
         launch_group(run_group(r), 0, e->st);
-        CHK(exscan(e->d_gcount.p + cnb[r], e->d_gscan.p + cnb[r], nsgrp + 1));
-        HIPCHK(hipMemcpyAsync(&nd[r], e->d_gscan.p + cnb[r] + nsgrp, 8, hipMemcpyDeviceToHost, e->st));
+        CHK(exscan(e->work.d_gcount.p + cnb[r], e->work.d_gscan.p + cnb[r], nsgrp + 1));
+        HIPCHK(hipMemcpyAsync(&nd[r], e->work.d_gscan.p + cnb[r] + nsgrp, 8, hipMemcpyDeviceToHost, e->st));
     }
     uint64_t nm = 0;
     // the other direction's groups: mirror images (spec 5b), or the reverse
     // searches of the shared candidate set (their own HSPs, in their order)
     const bool mirror = e->o.symmetric || e->share;
     if (e->share) {
-        G.cand_nh = e->d_cand_nh_r.p;
-        G.cand_hsp = e->d_cand_hsp_r.p;
-        G.cand_ovf = e->d_cand_ovf_r.p;
+        G.cand_nh = e->work.d_cand_nh_r.p;
+        G.cand_hsp = e->work.d_cand_hsp_r.p;
+        G.cand_ovf = e->work.d_cand_ovf_r.p;
     }
     if (mirror) {
         // the window of the tile's mirrored groups: every HSP is between a
@@ -1932,15 +1929,15 @@ static int group_stage(rc_engine *e, const TileCtx &C)
         G.mg0 = e->sample_gene_begin[b_lo];
         G.mgw = e->sample_gene_begin[b_hi] - e->sample_gene_begin[b_lo];
         const size_t nwin = (size_t)G.mgw * (size_t)G.msn;
-        CHK(e->d_mcnt.ensure(nwin + 1));
-        CHK(e->d_mcur.ensure(std::max<uint64_t>(C.n_cand, 1)));   // per candidate: its slots' start in its group
-        CHK(e->d_mscan.ensure(nwin + 1));
-        G.mcnt = e->d_mcnt.p;
-        G.mcur = e->d_mcur.p;
-        HIPCHK(hipMemsetAsync(e->d_mcnt.p, 0, (nwin + 1) * 4, e->st));
+        CHK(e->work.d_mcnt.ensure(nwin + 1));
+        CHK(e->work.d_mcur.ensure(std::max<uint64_t>(C.n_cand, 1)));   // per candidate: its slots' start in its group
+        CHK(e->work.d_mscan.ensure(nwin + 1));
+        G.mcnt = e->work.d_mcnt.p;
+        G.mcur = e->work.d_mcur.p;
+        HIPCHK(hipMemsetAsync(e->work.d_mcnt.p, 0, (nwin + 1) * 4, e->st));
         launch_group(G, 2, e->st);   // mirrored groups (spec 5b)
-        CHK(exscan(e->d_mcnt.p, e->d_mscan.p, nwin + 1));
-        HIPCHK(hipMemcpyAsync(&nm, e->d_mscan.p + nwin, 8, hipMemcpyDeviceToHost, e->st));
+        CHK(exscan(e->work.d_mcnt.p, e->work.d_mscan.p, nwin + 1));
+        HIPCHK(hipMemcpyAsync(&nm, e->work.d_mscan.p + nwin, 8, hipMemcpyDeviceToHost, e->st));
     }
     CHK(wait_st(e));
     uint64_t ndt = 0;
@@ -1951,29 +1948,29 @@ static int group_stage(rc_engine *e, const TileCtx &C)
     uint64_t base = e->hsp_used;
     for (size_t r = 0; r < R; r++) {
         GroupParams g = run_group(r);
-        g.cand_nh = e->d_cand_nh.p;
-        g.cand_hsp = e->d_cand_hsp.p;
-        g.cand_ovf = e->d_cand_ovf.p;
+        g.cand_nh = e->work.d_cand_nh.p;
+        g.cand_hsp = e->work.d_cand_hsp.p;
+        g.cand_ovf = e->work.d_cand_ovf.p;
         g.out = e->d_hsp.p;
         g.base = base;
         launch_group(g, 1, e->st);
         base += nd[r];
     }
     if (mirror) {
-        CHK(e->d_mkey.ensure(2 * nm + 2));
-        CHK(e->d_mbig.ensure(nm / 33 + 2));
+        CHK(e->work.d_mkey.ensure(2 * nm + 2));
+        CHK(e->work.d_mbig.ensure(nm / 33 + 2));
         HIPCHK(hipMemsetAsync(e->d_count.p + DC_MBIG, 0, sizeof(unsigned long long), e->st));
-        G.mscan = e->d_mscan.p;
+        G.mscan = e->work.d_mscan.p;
         G.out = e->d_hsp.p;
         G.mbase = base;
-        G.mkey = e->d_mkey.p;
-        G.mbig = e->d_mbig.p;
+        G.mkey = e->work.d_mkey.p;
+        G.mbig = e->work.d_mbig.p;
         G.mbig_n = e->d_count.p + DC_MBIG;
         launch_group(G, 3, e->st);
         launch_group(G, 4, e->st);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[4], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_GROUPS1], e->st));
     CHK(wait_st(e));
     e->hsp_used = nh;
     return RC_OK;
@@ -1991,15 +1988,15 @@ static int align_tile(rc_engine *e, int ti)
     CHK(seed_stage(e, C));
     CHK(extension_stage(e, C));
     CHK(group_stage(e, C));
-    e->tm.pack_ms += ev_ms(e, 0, 1);
-    e->tm.index_ms += ev_ms(e, 1, 2);
+    e->tm.pack_ms += ev_ms(e, EV_PACK0, EV_INDEX0);
+    e->tm.index_ms += ev_ms(e, EV_INDEX0, EV_ALIGN0);
     if (e->o.dust_level > 0 && !e->external) {
         float dms = 0;
-        if (hipEventElapsedTime(&dms, e->evd[0], e->evd[1]) == hipSuccess) e->tm.dust_ms += dms;
+        if (hipEventElapsedTime(&dms, e->evd[EVD_DUST0], e->evd[EVD_DUST1]) == hipSuccess) e->tm.dust_ms += dms;
     }
-    e->tm.align_ms += ev_ms(e, 2, 4);
-    e->tm.seed_kernel_ms += ev_ms(e, 3, 9);
-    e->tm.align_kernel_ms += ev_ms(e, 10, 11);
+    e->tm.align_ms += ev_ms(e, EV_ALIGN0, EV_GROUPS1);
+    e->tm.seed_kernel_ms += ev_ms(e, EV_SEED0, EV_SEED1);
+    e->tm.align_kernel_ms += ev_ms(e, EV_EXTEND0, EV_EXTEND1);
     return RC_OK;
 }
 
@@ -2020,11 +2017,11 @@ static int do_align(rc_engine *e)
 static int do_align_tiles(rc_engine *e)
 {
     if (e->external) {
-        HIPCHK(hipEventRecord(e->ev[0], e->st));
+        HIPCHK(hipEventRecord(e->ev[EV_PACK0], e->st));
         CHK(load_external(e));
-        HIPCHK(hipEventRecord(e->ev[1], e->st));
-        HIPCHK(hipEventSynchronize(e->ev[1]));
-        e->tm.align_ms = ev_ms(e, 0, 1);
+        HIPCHK(hipEventRecord(e->ev[EV_INDEX0], e->st));
+        HIPCHK(hipEventSynchronize(e->ev[EV_INDEX0]));
+        e->tm.align_ms = ev_ms(e, EV_PACK0, EV_INDEX0);
         e->aligned = true;
         return RC_OK;
     }
@@ -2044,14 +2041,14 @@ static int do_align_tiles(rc_engine *e)
     if (e->tiles_for != (int64_t)e->pair0 || e->tiles.empty()) {
         plan_tiles(e);
         e->tiles_for = (int64_t)e->pair0;
-        e->tile_loaded = -1;
+        e->work.tile_loaded = -1;
     }
     e->hsp_used = 0;
     e->n_seeds = e->n_cands = 0;
-    e->idx_bchunk = -1;   // every run builds its indexes and masks anew
+    e->work.idx_bchunk = -1;   // every run builds its indexes and masks anew
     // the tile loaded last goes first (its tables stay on the device)
     const int nt = (int)e->tiles.size();
-    const int first = (e->tile_loaded >= 0 && e->tile_loaded < nt) ? e->tile_loaded : 0;
+    const int first = (e->work.tile_loaded >= 0 && e->work.tile_loaded < nt) ? e->work.tile_loaded : 0;
     for (int k = 0; k < nt; k++) CHK(align_tile(e, (first + k) % nt));
     e->tm.tiles = (double)nt;
     e->n_hsps = e->hsp_used;
@@ -2068,17 +2065,17 @@ static int do_rbh(rc_engine *e)
     const uint64_t ni = e->item1 - e->item0;
     const size_t np = e->pair_a.size();
     e->finished = false;
-    HIPCHK(hipEventRecord(e->ev[5], e->st));
-    CHK(e->d_cnt4.ensure(4 * (ni + 1)));
+    HIPCHK(hipEventRecord(e->ev[EV_RBH0], e->st));
+    CHK(e->work.d_cnt4.ensure(4 * (ni + 1)));
     CHK(e->d_off4.ensure(4 * (ni + 1)));
-    HIPCHK(hipMemsetAsync(e->d_cnt4.p, 0, 4 * (ni + 1) * 4, e->st));
+    HIPCHK(hipMemsetAsync(e->work.d_cnt4.p, 0, 4 * (ni + 1) * 4, e->st));
     // the RBH selection loops' 8-byte view of the group table (bit score,
     // subject gene): r05, rbh_kernel 6.5 -> see DESIGN §4
-    CHK(e->d_hkey.ensure(std::max<uint64_t>(e->n_hsps, 1)));   // (n_hsps: aligned or imported)
-    launch_hkey(e->d_hsp.p, e->n_hsps, e->d_tx_gene.p, e->d_hkey.p, e->st);
+    CHK(e->work.d_hkey.ensure(std::max<uint64_t>(e->n_hsps, 1)));   // (n_hsps: aligned or imported)
+    launch_hkey(e->d_hsp.p, e->n_hsps, e->d_tx_gene.p, e->work.d_hkey.p, e->st);
     RbhParams R{};
     R.hsp = e->d_hsp.p;
-    R.hk = e->d_hkey.p;
+    R.hk = e->work.d_hkey.p;
     R.grp_off = e->d_grp_off.p;
     R.grp_cnt = e->d_grp_cnt.p;
     R.n_genes = (uint32_t)e->gene_sample.size();
@@ -2094,27 +2091,27 @@ static int do_rbh(rc_engine *e)
     R.keep_all = e->o.keep_all;
     R.item0 = e->item0;
     R.n_items = ni;
-    R.n_rows = e->d_cnt4.p;
-    R.n_fsel = e->d_cnt4.p + (ni + 1);
-    R.n_rsel = e->d_cnt4.p + 2 * (ni + 1);
-    R.n_edges = e->d_cnt4.p + 3 * (ni + 1);
+    R.n_rows = e->work.d_cnt4.p;
+    R.n_fsel = e->work.d_cnt4.p + (ni + 1);
+    R.n_rsel = e->work.d_cnt4.p + 2 * (ni + 1);
+    R.n_edges = e->work.d_cnt4.p + 3 * (ni + 1);
     // one pass over the groups: counts, and rows/edges in per-item slots
-    CHK(e->d_rows_tmp.ensure(std::max<uint64_t>(ni, 1) * RBH_RMAX));
-    CHK(e->d_edges_tmp.ensure(std::max<uint64_t>(ni, 1) * RBH_EMAX));
+    CHK(e->work.d_rows_tmp.ensure(std::max<uint64_t>(ni, 1) * RBH_RMAX));
+    CHK(e->work.d_edges_tmp.ensure(std::max<uint64_t>(ni, 1) * RBH_EMAX));
     HIPCHK(hipMemsetAsync(e->d_status.p + 1, 0, sizeof(unsigned int), e->st));
-    R.rows_tmp = e->d_rows_tmp.p;
-    R.edges_tmp = e->d_edges_tmp.p;
+    R.rows_tmp = e->work.d_rows_tmp.p;
+    R.edges_tmp = e->work.d_edges_tmp.p;
     R.ovf = e->d_status.p + 1;
     launch_rbh(R, 2, e->st);
     HIPCHK(hipGetLastError());
     for (int k = 0; k < 4; k++) {
         size_t tmp = 0;
-        const uint32_t *in = e->d_cnt4.p + k * (ni + 1);
+        const uint32_t *in = e->work.d_cnt4.p + k * (ni + 1);
         uint64_t *out = e->d_off4.p + k * (ni + 1);
         HIPCHK(rocprim::exclusive_scan(nullptr, tmp, in, out, (uint64_t)0, (size_t)ni + 1, rocprim::plus<uint64_t>(),
                                        e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::exclusive_scan(e->d_tmp.p, tmp, in, out, (uint64_t)0, (size_t)ni + 1,
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->work.d_tmp.p, tmp, in, out, (uint64_t)0, (size_t)ni + 1,
                                        rocprim::plus<uint64_t>(), e->st));
     }
     uint64_t tot[4] = {0, 0, 0, 0};
@@ -2139,9 +2136,9 @@ static int do_rbh(rc_engine *e)
     else
         launch_rbh_place(R, e->st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[6], e->st));
-    HIPCHK(hipEventSynchronize(e->ev[6]));
-    e->tm.rbh_ms = ev_ms(e, 5, 6);
+    HIPCHK(hipEventRecord(e->ev[EV_GRAPH0], e->st));
+    HIPCHK(hipEventSynchronize(e->ev[EV_GRAPH0]));
+    e->tm.rbh_ms = ev_ms(e, EV_RBH0, EV_GRAPH0);
     e->rbh_done = true;
     return RC_OK;
 }
@@ -2152,11 +2149,11 @@ static int do_graph(rc_engine *e)
 {
     if (!e->rbh_done) return fail(RC_E_STATE, "graph phase before rc_finish");
     CHK(set_device(e));
-    e->comp_valid = false;   // the per-component tables follow the graph
+    e->an.comp_valid = false;   // the per-component tables follow the graph
     const int N = (int)e->samples.size();
     const uint32_t n_genes = (uint32_t)e->gene_sample.size();
     const size_t np = e->pair_a.size();
-    HIPCHK(hipEventRecord(e->ev[6], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_GRAPH0], e->st));
     CHK(e->d_parent.ensure(n_genes));
     CHK(e->d_present.ensure(n_genes));
     CHK(e->d_cnodes.ensure(n_genes));
@@ -2170,7 +2167,7 @@ static int do_graph(rc_engine *e)
               e->d_present.p, e->d_cnodes.p,
               e->d_cedges.p, e->d_sample_present.p, e->d_ideal.p, e->d_stats.p, e->st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[7], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_REDUCE0], e->st));
     CHK(e->d_num.ensure(np));
     CHK(e->d_den.ensure(np));
     CHK(e->d_num_all.ensure(np));
@@ -2194,10 +2191,10 @@ static int do_graph(rc_engine *e)
         HIPCHK(hipMemcpyAsync(e->h_den_all.data(), e->d_den_all.p, np * 8, hipMemcpyDeviceToHost, e->st));
     }
     HIPCHK(hipMemcpyAsync(e->h_stats.data(), e->d_stats.p, 8 * 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipEventRecord(e->ev[8], e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_REDUCE1], e->st));
     HIPCHK(hipStreamSynchronize(e->st));
-    e->tm.graph_ms = ev_ms(e, 6, 7);
-    e->tm.reduce_ms = ev_ms(e, 7, 8);
+    e->tm.graph_ms = ev_ms(e, EV_GRAPH0, EV_REDUCE0);
+    e->tm.reduce_ms = ev_ms(e, EV_REDUCE0, EV_REDUCE1);
     e->tm.total_ms = e->tm.pack_ms + e->tm.index_ms + e->tm.align_ms + e->tm.rbh_ms + e->tm.graph_ms + e->tm.reduce_ms;
     e->finished = true;
     return RC_OK;
@@ -2261,8 +2258,8 @@ int rc_dust_mask(rc_engine *e, int32_t s, uint8_t *buf, uint64_t cap, uint64_t *
         return RC_OK;
     }
     // the mask of the loaded tile, where the sample sits at tile_pos[s]
-    if (e->tile_loaded < 0) return fail(RC_E_STATE, "no tile loaded");
-    const auto &ts = e->tiles[e->tile_loaded].samples;
+    if (e->work.tile_loaded < 0) return fail(RC_E_STATE, "no tile loaded");
+    const auto &ts = e->tiles[e->work.tile_loaded].samples;
     if (std::find(ts.begin(), ts.end(), s) == ts.end())
         return fail(RC_E_STATE, "the sample is not in the last alignment pass (tile)");
     if (!e->dmask_only.empty() && !e->dmask_only[s])
@@ -2271,7 +2268,7 @@ int rc_dust_mask(rc_engine *e, int32_t s, uint8_t *buf, uint64_t cap, uint64_t *
     const uint64_t b0 = e->tile_pos[s];
     const uint64_t w0 = b0 >> 6, w1 = (b0 + S.nbases + 63) >> 6;
     std::vector<uint64_t> words(w1 - w0);
-    HIPCHK(hipMemcpy(words.data(), e->d_dmask.p + 1 + w0, words.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(words.data(), e->work.d_dmask.p + 1 + w0, words.size() * 8, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < S.nbases; i++) {
         const uint64_t p = b0 + i;
         buf[i] = (uint8_t)((words[(p >> 6) - w0] >> (p & 63)) & 1);
@@ -2325,7 +2322,7 @@ int rc_dust_masks(rc_engine *e, const int32_t *samples, int32_t n, uint64_t *out
     if (e->tiles_for != (int64_t)e->pair0 || e->tiles.empty()) {
         plan_tiles(e);
         e->tiles_for = (int64_t)e->pair0;
-        e->tile_loaded = -1;
+        e->work.tile_loaded = -1;
     }
     // the shard's own alignment tile when it is a single tile holding these
     // samples (its tables stay loaded for rc_align), else tiles of these
@@ -2358,15 +2355,15 @@ int rc_dust_masks(rc_engine *e, const int32_t *samples, int32_t n, uint64_t *out
             rc_engine::Tile T;
             T.samples = chunks[c];
             e->tiles.push_back(T);
-            e->tile_loaded = -1;
+            e->work.tile_loaded = -1;
             ti = (int)e->tiles.size() - 1;
         }
         rc = load_tile(e, ti);
         if (rc == RC_OK) rc = pack_tile(e);
         if (rc == RC_OK && dust) {
             const size_t mw = (e->tile_total >> 6) + 4;
-            rc = e->d_dmask.ensure(mw);
-            if (rc == RC_OK && hipMemsetAsync(e->d_dmask.p, 0, mw * 8, e->st) != hipSuccess)
+            rc = e->work.d_dmask.ensure(mw);
+            if (rc == RC_OK && hipMemsetAsync(e->work.d_dmask.p, 0, mw * 8, e->st) != hipSuccess)
                 rc = fail(RC_E_HIP, "hipMemsetAsync");
             if (rc == RC_OK) rc = dust_samples(e, chunks[c], e->st);
         }
@@ -2377,7 +2374,7 @@ int rc_dust_masks(rc_engine *e, const int32_t *samples, int32_t n, uint64_t *out
             for (uint64_t w0 : oof[s]) {
                 hipError_t h = hipSuccess;
                 if (dust) {
-                    h = hipMemcpyAsync(out + w0, e->d_dmask.p + 1 + (e->tile_pos[s] >> 6), nw * 8,
+                    h = hipMemcpyAsync(out + w0, e->work.d_dmask.p + 1 + (e->tile_pos[s] >> 6), nw * 8,
                                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->st);
                 } else if (on_device) {
                     h = hipMemsetAsync(out + w0, 0, nw * 8, e->st);
@@ -2390,7 +2387,7 @@ int rc_dust_masks(rc_engine *e, const int32_t *samples, int32_t n, uint64_t *out
         if (rc == RC_OK && hipStreamSynchronize(e->st) != hipSuccess) rc = fail(RC_E_HIP, "hipStreamSynchronize");
         if (!own) {
             e->tiles.pop_back();
-            e->tile_loaded = -1;
+            e->work.tile_loaded = -1;
         }
     }
     if (own) {   // the loaded tile's masks now hold the listed samples only
@@ -2413,7 +2410,7 @@ int rc_dust_masks(rc_engine *e, const int32_t *samples, int32_t n, uint64_t *out
             out[o - 1] &= keep;
         }
     }
-    e->idx_bchunk = -1;
+    e->work.idx_bchunk = -1;
     return rc;
 }
 
@@ -2537,43 +2534,17 @@ int rc_import_edge_parts(rc_engine *e, const void *buf, const uint64_t *counts, 
     return do_graph(e);
 }
 
-// Free the alignment working set of a finished run: tile copies, indexes,
-// seeds, candidates, extension and grouping scratch. What the results need
-// stays (inputs, HSP store and groups, table rows, edges, graph arrays); the
-// next rc_align allocates the rest again.
+// Free the alignment working set of a finished run (struct Work: tile copies,
+// indexes, seeds, candidates, extension and grouping scratch). What the
+// results need stays (inputs, HSP store and groups, table rows, edges, graph
+// arrays); the next rc_align allocates the rest again.
 int rc_trim(rc_engine *e)
 {
     if (!e) return fail(RC_E_ARG, "null engine");
     CHK(set_device(e));
     HIPCHK(hipStreamSynchronize(e->st));
     HIPCHK(hipStreamSynchronize(e->st2));
-    e->d_tile_ascii.release(); e->d_tile_tx.release(); e->d_tile_itx.release(); e->d_tile_gid.release();
-    e->d_tile_segs.release(); e->d_tile_send.release();
-    e->d_F.release(); e->d_RC.release(); e->d_AF.release(); e->d_ARC.release();
-    e->d_kpos_off.release(); e->d_kcnt.release(); e->d_kpos_rel.release();
-    e->d_tile_masked.release(); e->d_ment.release(); e->d_ment2.release(); e->d_mbucket.release();
-    e->d_rseeds.release(); e->d_rseed_gene.release(); e->d_rs_key.release(); e->d_rs_idx.release();
-    e->d_rs_range.release(); e->d_rctr.release(); e->d_rtmask.release(); e->d_trange.release(); e->d_rtrange.release();
-    e->d_ent.release(); e->d_ent2.release(); e->d_sort_scratch.release();
-    e->d_range_off.release(); e->d_range_list.release();
-    e->d_sort_status.release(); e->d_bucket.release(); e->d_pos_tx.release(); e->d_sample_pos.release();
-    e->d_txstart.release(); e->d_dmask.release(); e->d_dust_scratch.release(); e->d_dust_events.release();
-    e->d_prof.release(); e->d_tmp.release(); e->d_seeds.release(); e->d_cands.release();
-    e->d_cand_hsp.release(); e->d_ovf.release(); e->d_cand_nh.release(); e->d_cand_box.release(); e->d_hkey.release();
-    e->d_cand_box2.release(); e->d_cand_hsp_r.release(); e->d_cand_nh_r.release(); e->d_cand_ovf_r.release();
-    e->d_defer_r.release(); e->d_list2.release(); e->d_wide0.release(); e->d_wide1.release(); e->d_resume.release();
-    e->d_later.release(); e->d_lbox0.release(); e->d_lbox1.release(); e->d_lvc0.release(); e->d_lvc1.release();
-    e->d_llist0.release(); e->d_llist1.release(); e->d_lact0.release(); e->d_lact1.release(); e->d_lcnt.release();
-    e->d_lfull0.release(); e->d_lfull1.release();
-    e->d_rows_tmp.release(); e->d_edges_tmp.release(); e->d_cand_ovf.release(); e->d_gc_off.release();
-    e->d_gc_cnt.release(); e->d_gcount.release(); e->d_defer.release(); e->d_gscan.release();
-    e->d_mscan.release(); e->d_mkey.release(); e->d_tmask.release(); e->d_mbig.release(); e->d_mcnt.release();
-    e->d_mcur.release(); e->d_big_out.release(); e->d_big_list.release(); e->d_big_retry.release();
-    e->d_big_seeds.release(); e->d_big_seg.release(); e->d_big_segT.release(); e->d_cnt4.release();
-    e->tile_loaded = -1;   // (rc_dust_mask reads a loaded tile: none now)
-    e->idx_bchunk = -1;
-    e->mnear_cap = 0;
-    e->res_cap = 0;
+    e->work = rc_engine::Work{};
     return RC_OK;
 }
 

@@ -406,8 +406,8 @@ static int edge_slots(rc_engine *e, GraphSlots &G)
         HIPCHK(hipGetLastError());
         size_t tmp = 0;
         HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, k0.p, k1.p, v0.p, v1.p, (size_t)n, 0u, 32u, e->st));
-        CHK(e->d_tmp.ensure(tmp));
-        HIPCHK(rocprim::radix_sort_pairs(e->d_tmp.p, tmp, k0.p, k1.p, v0.p, v1.p, (size_t)n, 0u, 32u, e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::radix_sort_pairs(e->work.d_tmp.p, tmp, k0.p, k1.p, v0.p, v1.p, (size_t)n, 0u, 32u, e->st));
         uint32_t last = 0;
         HIPCHK(hipMemcpyAsync(&last, k1.p + n - 1, 4, hipMemcpyDeviceToHost, e->st));
         // the (a, b) arrays reuse the sort's input buffers

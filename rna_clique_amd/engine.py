@@ -295,6 +295,36 @@ class Engine:
         nat.check(nat.lib().rc_component_sums(self._h, None, None, 0, ctypes.byref(c), ctypes.byref(p)))
         return c.value
 
+    # ------------------------------------ arguments of the replicate analyses
+    @staticmethod
+    def _weights(weights):
+        """Per-component weights as a contiguous uint16 (R, C) array."""
+        w = np.asarray(weights)
+        if w.ndim != 2:
+            raise ValueError("weights must have shape (replicates, components)")
+        if w.dtype != np.uint16:
+            if w.dtype.kind not in "iu":
+                raise TypeError("weights must be integers")
+            if w.size and (w.min() < 0 or w.max() > 65535):
+                raise ValueError("weights must lie in 0..65535")
+        return np.ascontiguousarray(w, dtype=np.uint16)
+
+    def _order(self, order):
+        """Sample ids as an int32 array; default: sorted label order."""
+        if order is None:
+            order = sorted(range(len(self.labels)), key=lambda i: self.labels[i])
+        return np.ascontiguousarray(order, dtype=np.int32)
+
+    @staticmethod
+    def _matrices(matrices):
+        """Distance matrices (R, N, N) or (N, N) as float64 (R, N, N)."""
+        d = np.ascontiguousarray(matrices, dtype=np.float64)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1] != d.shape[2]:
+            raise ValueError("matrices must have shape (replicates, N, N)")
+        return d
+
     def resample(self, weights, order=None, sums=False, *, allow_nan=False):
         """Replicate distance matrices from per-component weights (R, C),
         integers in 0..65535: replicate r's sums are sum_c weights[r, c] *
@@ -304,19 +334,8 @@ class Engine:
         without rows, unless allow_nan (its entries are then NaN). A bootstrap over components draws
         each row from a multinomial (similarity.bootstrap_weights); a
         delete-one jackknife or a block deletion is a 0/1 matrix."""
-        w = np.asarray(weights)
-        if w.ndim != 2:
-            raise ValueError("weights must have shape (replicates, components)")
-        if w.dtype != np.uint16:
-            if w.dtype.kind not in "iu":
-                raise TypeError("weights must be integers")
-            if w.size and (w.min() < 0 or w.max() > 65535):
-                raise ValueError("weights must lie in 0..65535")
-        w = np.ascontiguousarray(w, dtype=np.uint16)
+        w, order = self._weights(weights), self._order(order)
         n = len(self.labels)
-        if order is None:
-            order = sorted(range(n), key=lambda i: self.labels[i])
-        order = np.ascontiguousarray(order, dtype=np.int32)
         m, r = len(order), w.shape[0]
         p = n * (n - 1) // 2
         out = np.zeros((r, m, m), dtype=np.float64)
@@ -361,11 +380,7 @@ class Engine:
         Raises NativeError(RC_E_NO_IDEAL) when a matrix has a non-finite
         entry, unless allow_nan (that tree is then flagged in `valid`)."""
         from .tree import NJResult
-        d = np.ascontiguousarray(matrices, dtype=np.float64)
-        if d.ndim == 2:
-            d = d[None]
-        if d.ndim != 3 or d.shape[1] != d.shape[2]:
-            raise ValueError("matrices must have shape (replicates, N, N)")
+        d = self._matrices(matrices)
         r, m = d.shape[0], d.shape[1]
         ref, bufs = self._nj_buffers(r, m, ref_splits)
         nv = ctypes.c_uint32()
@@ -381,19 +396,7 @@ class Engine:
         NativeError(RC_E_NO_IDEAL) when a replicate has a pair without rows,
         unless allow_nan (that tree is then flagged in `valid`)."""
         from .tree import NJResult
-        w = np.asarray(weights)
-        if w.ndim != 2:
-            raise ValueError("weights must have shape (replicates, components)")
-        if w.dtype != np.uint16:
-            if w.dtype.kind not in "iu":
-                raise TypeError("weights must be integers")
-            if w.size and (w.min() < 0 or w.max() > 65535):
-                raise ValueError("weights must lie in 0..65535")
-        w = np.ascontiguousarray(w, dtype=np.uint16)
-        n = len(self.labels)
-        if order is None:
-            order = sorted(range(n), key=lambda i: self.labels[i])
-        order = np.ascontiguousarray(order, dtype=np.int32)
+        w, order = self._weights(weights), self._order(order)
         m, r = len(order), w.shape[0]
         ref, bufs = self._nj_buffers(r, m, ref_splits)
         nv = ctypes.c_uint32()
@@ -425,11 +428,7 @@ class Engine:
         NativeError(RC_E_LIMIT) when one has not converged in max_sweeps
         (0 = the default, 30) sweeps."""
         from .pcoa import PCoAEigen
-        d = np.ascontiguousarray(matrices, dtype=np.float64)
-        if d.ndim == 2:
-            d = d[None]
-        if d.ndim != 3 or d.shape[1] != d.shape[2]:
-            raise ValueError("matrices must have shape (replicates, N, N)")
+        d = self._matrices(matrices)
         r, m = d.shape[0], d.shape[1]
         k, bufs, ptrs = self._pcoa_buffers(r, m, k)
         code = nat.lib().rc_pcoa(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, k, int(max_sweeps), *ptrs)
@@ -444,19 +443,7 @@ class Engine:
         labels[i]. Errors as pcoa(); RC_E_NO_IDEAL: a replicate has a pair
         without rows."""
         from .pcoa import PCoAEigen
-        w = np.asarray(weights)
-        if w.ndim != 2:
-            raise ValueError("weights must have shape (replicates, components)")
-        if w.dtype != np.uint16:
-            if w.dtype.kind not in "iu":
-                raise TypeError("weights must be integers")
-            if w.size and (w.min() < 0 or w.max() > 65535):
-                raise ValueError("weights must lie in 0..65535")
-        w = np.ascontiguousarray(w, dtype=np.uint16)
-        n = len(self.labels)
-        if order is None:
-            order = sorted(range(n), key=lambda i: self.labels[i])
-        order = np.ascontiguousarray(order, dtype=np.int32)
+        w, order = self._weights(weights), self._order(order)
         m, r = len(order), w.shape[0]
         k, bufs, ptrs = self._pcoa_buffers(r, m, k)
         vp = ctypes.c_void_p

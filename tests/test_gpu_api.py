@@ -660,8 +660,9 @@ def test_rccl_exchange_world1(native):
 
 def test_trim_and_edge_parts(native):
     """rc_trim frees the alignment working set of a finished run (device
-    bytes drop; rows, HSPs and distances stay readable and unchanged; the
-    next run allocates it again and gives the same results), and
+    bytes drop, a second trim frees nothing more; timings, rows, HSPs and
+    distances stay readable and unchanged; the next run allocates it again and
+    gives the same results, also after another trim), and
     rc_import_edge_parts takes padded blocks -- from the host or the device,
     device records range-checked on the device."""
     import torch
@@ -676,10 +677,17 @@ def test_trim_and_edge_parts(native):
     hs = eng.hsps(3, 1).tobytes()
     dist0 = eng.distance()[1]
     edges = eng.export_edges()
-    before = eng.timings()["dev_bytes"]
+    t0 = eng.timings()
+    before = t0["dev_bytes"]
     eng.trim()
-    after = eng.timings()["dev_bytes"]
+    t1 = eng.timings()
+    after = t1["dev_bytes"]
     assert after < before - (64 << 20), (before, after)
+    eng.trim()   # nothing left to free
+    assert eng.timings()["dev_bytes"] == after
+    # the finished run's timings are still there (a trim only moves dev_bytes)
+    assert t1["total_ms"] > 0 and {k: v for k, v in t1.items() if k != "dev_bytes"} == \
+        {k: v for k, v in t0.items() if k != "dev_bytes"}
     assert {p: eng.pair_rows(*p).tobytes() for p in pairs} == rows and eng.hsps(3, 1).tobytes() == hs
     assert np.array_equal(eng.distance()[1], dist0)
     with pytest.raises(NativeError):
@@ -707,4 +715,6 @@ def test_trim_and_edge_parts(native):
         eng.import_edge_parts(bad.ravel(), counts, stride)
     eng.run()   # the working set allocated again
     assert {p: eng.pair_rows(*p).tobytes() for p in pairs} == rows and eng.hsps(3, 1).tobytes() == hs
+    assert np.array_equal(eng.distance()[1], dist0)
+    eng.trim()   # and freed again
     assert np.array_equal(eng.distance()[1], dist0)
