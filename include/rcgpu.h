@@ -326,6 +326,31 @@ int rc_component_sums(rc_engine *eng, int64_t *num, int64_t *den, uint64_t cap_c
 int rc_resample(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
                 int32_t n, double *out, int64_t *num, int64_t *den);
 
+/* ---- component census (after rc_run / rc_finish / rc_import_edges) -------
+ * Every connected component over the graph's nodes (the endpoints of graph
+ * edges and the isolated nodes; sums-only records join nothing), ideal or
+ * not, numbered 0..K-1 in ascending order of its lowest global gene index --
+ * the rule of the ideal component ids, so the ideal components keep their
+ * relative order; not the reference's order (component_subgraphs follows
+ * graph insertion order). Per component: root (the lowest member), nodes,
+ * edges (graph edges between two different genes: the count the ideal test
+ * uses) and samples (distinct samples among the members). The members are all
+ * nodes sorted by (component, global gene index), so component c owns entries
+ * [off[c], off[c] + nodes[c]) with off the exclusive prefix sum of nodes, in
+ * ascending sample. A component is ideal iff nodes == sample_count and
+ * 2 * edges == nodes * (nodes - 1). The census is built on the device by the
+ * first of these calls after a graph phase and kept there (16 bytes per
+ * component, 4 per node) until the next one; rc_trim keeps it.
+ *
+ * rc_components: n_comp rows in five arrays of cap entries each. All NULL
+ * queries n_comp; some but not all NULL is RC_E_ARG; cap < n_comp is
+ * RC_E_CAPACITY. */
+int rc_components(rc_engine *eng, int32_t *root_sample, int32_t *root_gene, int64_t *nodes, int64_t *edges,
+                  int32_t *samples, uint64_t cap, uint64_t *n_comp);
+/* The members as (sample, gene id), n_nodes entries (rc_graph_stats' nodes).
+ * NULL buffers query n_nodes. */
+int rc_component_members(rc_engine *eng, int32_t *sample, int32_t *gene, uint64_t cap, uint64_t *n_nodes);
+
 /* ---- neighbour-joining trees and split support ---------------------------
  * Saitou & Nei's neighbour joining in float64 with a fixed operation order, so
  * that a tree is reproducible bit for bit: of matrix

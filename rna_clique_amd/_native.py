@@ -136,6 +136,8 @@ SIGNATURES = {
     "rc_distance_subset": (ctypes.c_int, [VP, VP, ctypes.c_int32, VP]),
     "rc_ideal_components": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_int32)]),
     "rc_component_sums": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64)]),
+    "rc_components": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]),
+    "rc_component_members": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]),
     "rc_resample": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, VP, VP, VP]),
     "rc_nj": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int32, VP, VP, VP, VP, VP, ctypes.c_int32, VP, VP]),
     "rc_resample_trees": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, VP, VP, VP, VP,

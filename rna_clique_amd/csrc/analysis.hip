@@ -86,7 +86,116 @@ static int build_components(rc_engine *e)
     return RC_OK;
 }
 
+// The census of the finished graph phase, built once per graph: the census id
+// of every root (the exclusive scan of the root flag), the members (sorted
+// (census id, gene) keys of the present genes) and the rows root, nodes,
+// edges, samples. They stay on the device until the next do_graph.
+static int build_census(rc_engine *e)
+{
+    if (!e->finished) return fail(RC_E_STATE, "no results yet");
+    CHK(set_device(e));
+    if (e->an.census_valid) return RC_OK;
+    const uint32_t ng = (uint32_t)e->gene_sample.size();
+    uint64_t K = 0;
+    unsigned long long present = 0;
+    DBuf<uint32_t> flag, rank;
+    DBuf<uint64_t> k0, k1;
+    CHK(e->an.d_cstat.ensure(CS_N));
+    if (ng) {
+        CHK(flag.ensure(ng));
+        CHK(rank.ensure(ng));
+        CHK(k0.ensure(ng));
+        CHK(k1.ensure(ng));
+        HIPCHK(hipMemsetAsync(e->an.d_cstat.p + CS_MEMBERS, 0, sizeof(unsigned long long), e->st));
+        launch_census_flags(e->d_parent.p, e->d_present.p, ng, flag.p, e->st);
+        HIPCHK(hipGetLastError());
+        size_t tmp = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, flag.p, rank.p, 0u, (size_t)ng, rocprim::plus<uint32_t>(), e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->work.d_tmp.p, tmp, flag.p, rank.p, 0u, (size_t)ng,
+                                       rocprim::plus<uint32_t>(), e->st));
+        launch_census_keys(e->d_parent.p, e->d_present.p, rank.p, ng, k0.p, e->an.d_cstat.p + CS_MEMBERS, e->st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(rocprim::radix_sort_keys(nullptr, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::radix_sort_keys(e->work.d_tmp.p, tmp, k0.p, k1.p, (size_t)ng, 0u, 64u, e->st));
+        uint32_t last_rank = 0, last_flag = 0;
+        HIPCHK(hipMemcpyAsync(&last_rank, rank.p + ng - 1, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&last_flag, flag.p + ng - 1, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&present, e->an.d_cstat.p + CS_MEMBERS, 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipStreamSynchronize(e->st));
+        K = (uint64_t)last_rank + last_flag;
+    }
+    if (K != e->h_stats[0]) return fail(RC_E_STATE, "the root scan disagrees with the component count");
+    if (present != e->h_stats[3]) return fail(RC_E_STATE, "the member keys disagree with the node count");
+    CHK(e->an.d_zroot.ensure(K));
+    CHK(e->an.d_znodes.ensure(K));
+    CHK(e->an.d_zedges.ensure(K));
+    CHK(e->an.d_zsamples.ensure(K));
+    CHK(e->an.d_zmember.ensure(present));
+    if (K) {
+        launch_census_table(flag.p, rank.p, e->d_cnodes.p, e->d_cedges.p, ng, e->an.d_zroot.p, e->an.d_znodes.p,
+                            e->an.d_zedges.p, e->an.d_zsamples.p, e->st);
+        launch_census_members(k1.p, present, e->d_gene_sample.p, e->an.d_zmember.p, e->an.d_zsamples.p, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(e->st));   // flag, rank, k0, k1 go out of scope
+    e->an.census_n = K;
+    e->an.census_members = present;
+    e->an.census_valid = true;
+    return RC_OK;
+}
+
 extern "C" {
+
+int rc_components(rc_engine *e, int32_t *root_sample, int32_t *root_gene, int64_t *nodes, int64_t *edges,
+                  int32_t *samples, uint64_t cap, uint64_t *n_comp)
+{
+    if (!e || !n_comp) return fail(RC_E_ARG, "null argument");
+    CHK(build_census(e));
+    const uint64_t K = e->an.census_n;
+    *n_comp = K;
+    const int given = !!root_sample + !!root_gene + !!nodes + !!edges + !!samples;
+    if (!given) return RC_OK;
+    if (given != 5) return fail(RC_E_ARG, "null argument");
+    if (cap < K) return fail(RC_E_CAPACITY, "buffer too small");
+    if (!K) return RC_OK;
+    std::vector<uint32_t> h[4];
+    const uint32_t *src[4] = {e->an.d_zroot.p, e->an.d_znodes.p, e->an.d_zedges.p, e->an.d_zsamples.p};
+    for (int i = 0; i < 4; i++) {
+        h[i].resize(K);
+        HIPCHK(hipMemcpyAsync(h[i].data(), src[i], K * 4, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(hipStreamSynchronize(e->st));
+    for (uint64_t c = 0; c < K; c++) {
+        root_sample[c] = e->gene_sample[h[0][c]];
+        root_gene[c] = e->gene_id[h[0][c]];
+        nodes[c] = h[1][c];
+        edges[c] = h[2][c];
+        samples[c] = (int32_t)h[3][c];
+    }
+    return RC_OK;
+}
+
+int rc_component_members(rc_engine *e, int32_t *sample, int32_t *gene, uint64_t cap, uint64_t *n_nodes)
+{
+    if (!e || !n_nodes) return fail(RC_E_ARG, "null argument");
+    CHK(build_census(e));
+    const uint64_t nm = e->an.census_members;
+    *n_nodes = nm;
+    if (!sample && !gene) return RC_OK;
+    if (!sample || !gene) return fail(RC_E_ARG, "null argument");
+    if (cap < nm) return fail(RC_E_CAPACITY, "buffer too small");
+    if (!nm) return RC_OK;
+    std::vector<uint32_t> m(nm);
+    HIPCHK(hipMemcpyAsync(m.data(), e->an.d_zmember.p, nm * 4, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    for (uint64_t i = 0; i < nm; i++) {
+        sample[i] = e->gene_sample[m[i]];
+        gene[i] = e->gene_id[m[i]];
+    }
+    return RC_OK;
+}
 
 int rc_ideal_components(rc_engine *e, int32_t *sample, int32_t *gene, uint64_t cap_nodes, uint64_t *n_comp,
                         int32_t *sample_count)

@@ -1,5 +1,6 @@
 // Per-component tables of a finished graph phase and the resampling product
-// over them (rc_ideal_components, rc_component_sums, rc_resample).
+// over them (rc_ideal_components, rc_component_sums, rc_resample), and the
+// census of every component (rc_components, rc_component_members; below).
 //
 // Component ids: the ideal components are numbered 0..C-1 in ascending order
 // of their union-find root. cc_hook_kernel always hooks the larger root under
@@ -210,8 +211,122 @@ __global__ void resample_distance_kernel(const ull *__restrict__ num, const ull 
 }
 
 // ------------------------------------------------------------------------
+// component census (rc_components, rc_component_members)
+//
+// Every connected component over the present genes, numbered 0..K-1 in
+// ascending order of its root (its lowest global gene index): the census id of
+// a root is the exclusive prefix sum of census_flag_kernel's flag. These
+// kernels only read what the graph phase left (parent, present, cnodes,
+// cedges, gene_sample).
+// ------------------------------------------------------------------------
+
+// flag[v] = 1 at the root of a component of present genes
+__global__ void census_flag_kernel(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ present,
+                                   uint32_t n, uint32_t *__restrict__ flag)
+{
+    for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < n; v += (uint64_t)gridDim.x * blockDim.x)
+        flag[v] = parent[v] == v && present[v] ? 1u : 0u;
+}
+
+// comp_key_kernel for every present gene: (census id << 32 | gene), all ones
+// for the absent ones. Sorted ascending, the first n_present keys are the
+// members, component by component, in ascending gene index. counter[0] +=
+// present genes.
+__global__ void census_key_kernel(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ present,
+                                  const uint32_t *__restrict__ rank, uint32_t n, uint64_t *__restrict__ key,
+                                  ull *counter)
+{
+    ull mine = 0;
+    for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < n; v += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t k = ~0ull;
+        if (present[v]) {
+            k = (uint64_t)rank[parent[v]] << 32 | v;
+            mine++;
+        }
+        key[v] = k;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(counter, mine);
+}
+
+// The table's gathered columns, one thread per gene: a root scatters itself,
+// cnodes and cedges to its census id. samples[] is zeroed here for
+// census_member_kernel.
+__global__ void census_table_kernel(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank,
+                                    const uint32_t *__restrict__ cnodes, const uint32_t *__restrict__ cedges,
+                                    uint32_t n, uint32_t *__restrict__ root, uint32_t *__restrict__ nodes,
+                                    uint32_t *__restrict__ edges, uint32_t *__restrict__ samples)
+{
+    for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < n; v += (uint64_t)gridDim.x * blockDim.x) {
+        if (!flag[v]) continue;
+        const uint32_t c = rank[v];
+        root[c] = (uint32_t)v;
+        nodes[c] = cnodes[v];
+        edges[c] = cedges[v];
+        samples[c] = 0;
+    }
+}
+
+// One pass over the sorted members: members[i] = gene of key i, and
+// samples[c] += 1 for every member that is the first of its sample in its
+// component -- it opens the component's slice, or its predecessor is of
+// another sample (genes are numbered sample-major, so a component's members
+// are in ascending sample). A component gets one atomic per sample it holds,
+// whatever its size: a giant component is as cheap as a small one. Integer
+// sums: the result does not depend on the order of the atomics.
+__global__ void census_member_kernel(const uint64_t *__restrict__ key, uint64_t n_members,
+                                     const int32_t *__restrict__ gene_sample, uint32_t *__restrict__ members,
+                                     uint32_t *samples)
+{
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_members;
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = key[i];
+        const uint32_t v = (uint32_t)k, c = (uint32_t)(k >> 32);
+        members[i] = v;
+        bool first = i == 0;
+        if (!first) {
+            const uint64_t kp = key[i - 1];
+            first = (uint32_t)(kp >> 32) != c || gene_sample[(uint32_t)kp] != gene_sample[v];
+        }
+        if (first) atomicAdd(&samples[c], 1u);
+    }
+}
+
+// ------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------
+
+void launch_census_flags(const uint32_t *parent, const uint32_t *present, uint32_t n, uint32_t *flag, hipStream_t st)
+{
+    if (!n) return;
+    hipLaunchKernelGGL(census_flag_kernel, dim3(comp_grid(n, 256)), dim3(256), 0, st, parent, present, n, flag);
+}
+
+void launch_census_keys(const uint32_t *parent, const uint32_t *present, const uint32_t *rank, uint32_t n,
+                        uint64_t *key, ull *counter, hipStream_t st)
+{
+    if (!n) return;
+    hipLaunchKernelGGL(census_key_kernel, dim3(comp_grid(n, 256)), dim3(256), 0, st, parent, present, rank, n, key,
+                       counter);
+}
+
+void launch_census_table(const uint32_t *flag, const uint32_t *rank, const uint32_t *cnodes, const uint32_t *cedges,
+                         uint32_t n, uint32_t *root, uint32_t *nodes, uint32_t *edges, uint32_t *samples,
+                         hipStream_t st)
+{
+    if (!n) return;
+    hipLaunchKernelGGL(census_table_kernel, dim3(comp_grid(n, 256)), dim3(256), 0, st, flag, rank, cnodes, cedges, n,
+                       root, nodes, edges, samples);
+}
+
+void launch_census_members(const uint64_t *key, uint64_t n_members, const int32_t *gene_sample, uint32_t *members,
+                           uint32_t *samples, hipStream_t st)
+{
+    if (!n_members) return;
+    hipLaunchKernelGGL(census_member_kernel, dim3(comp_grid(n_members, 256)), dim3(256), 0, st, key, n_members,
+                       gene_sample, members, samples);
+}
 
 void launch_comp_keys(const uint32_t *parent, const uint32_t *present, const uint8_t *ideal, const uint32_t *rank,
                       uint32_t n, uint64_t *key, ull *counter, hipStream_t st)

@@ -377,6 +377,12 @@ struct rc_engine {
         DBuf<unsigned long long> d_cnum, d_cden, d_cstat, d_rnum, d_rden;
         DBuf<uint2> d_ccell;
         DBuf<uint16_t> d_rweight;
+        // The census of every component (build_census, with a validity flag of
+        // its own: whatever clears comp_valid clears census_valid too): the
+        // rows [K] root, nodes, edges, samples and the members [present genes]
+        bool census_valid = false;
+        uint64_t census_n = 0, census_members = 0;
+        DBuf<uint32_t> d_zroot, d_znodes, d_zedges, d_zsamples, d_zmember;
         // neighbour joining (nj.hip): input matrices of rc_nj, the trees, the
         // reference splits with their support (n_ref counters, then n_valid) and
         // the workspace of the trees too large for LDS

@@ -2150,6 +2150,7 @@ static int do_graph(rc_engine *e)
     if (!e->rbh_done) return fail(RC_E_STATE, "graph phase before rc_finish");
     CHK(set_device(e));
     e->an.comp_valid = false;   // the per-component tables follow the graph
+    e->an.census_valid = false;
     const int N = (int)e->samples.size();
     const uint32_t n_genes = (uint32_t)e->gene_sample.size();
     const size_t np = e->pair_a.size();

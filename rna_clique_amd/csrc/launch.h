@@ -48,6 +48,12 @@ bool launch_resample(const uint2 *, const uint16_t *, uint64_t, uint64_t, uint32
                      unsigned long long *, hipStream_t);
 void launch_resample_distance(const unsigned long long *, const unsigned long long *, const int32_t *, const int32_t *,
                               int, int, uint64_t, uint64_t, double *, unsigned int *, hipStream_t);
+void launch_census_flags(const uint32_t *, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
+void launch_census_keys(const uint32_t *, const uint32_t *, const uint32_t *, uint32_t, uint64_t *,
+                        unsigned long long *, hipStream_t);
+void launch_census_table(const uint32_t *, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t, uint32_t *,
+                         uint32_t *, uint32_t *, uint32_t *, hipStream_t);
+void launch_census_members(const uint64_t *, uint64_t, const int32_t *, uint32_t *, uint32_t *, hipStream_t);
 // nj.hip
 size_t nj_lds_bytes(bool, int, int);
 hipError_t launch_nj(bool, const double *, int, int, int, double *, uint64_t *, int32_t *, double *, uint64_t *,

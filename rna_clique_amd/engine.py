@@ -295,6 +295,38 @@ class Engine:
         nat.check(nat.lib().rc_component_sums(self._h, None, None, 0, ctypes.byref(c), ctypes.byref(p)))
         return c.value
 
+    # ------------------------------------------------------ component census
+    def components(self):
+        """One row per connected component of the graph, ideal or not, in
+        ascending order of its lowest (sample id, gene id) node: a dict of
+        root_sample, root_gene, samples (int32) and nodes, edges (int64)
+        arrays of length K (rc_components; census.ComponentTable derives the
+        rest)."""
+        L = nat.lib()
+        k = ctypes.c_uint64()
+        nat.check(L.rc_components(self._h, None, None, None, None, None, 0, ctypes.byref(k)))
+        out = {"root_sample": np.zeros(k.value, dtype=np.int32), "root_gene": np.zeros(k.value, dtype=np.int32),
+               "nodes": np.zeros(k.value, dtype=np.int64), "edges": np.zeros(k.value, dtype=np.int64),
+               "samples": np.zeros(k.value, dtype=np.int32)}
+        if k.value:
+            nat.check(L.rc_components(self._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in out.values()),
+                                      k.value, ctypes.byref(k)))
+        return out
+
+    def component_members(self):
+        """(sample, gene) int32 arrays: every graph node, sorted by
+        (component, sample id, gene id). Component c of components() owns
+        [off[c], off[c] + nodes[c]), off the exclusive prefix sum of nodes."""
+        L = nat.lib()
+        n = ctypes.c_uint64()
+        nat.check(L.rc_component_members(self._h, None, None, 0, ctypes.byref(n)))
+        s = np.zeros(n.value, dtype=np.int32)
+        g = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            nat.check(L.rc_component_members(self._h, s.ctypes.data_as(ctypes.c_void_p),
+                                             g.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return s, g
+
     # ------------------------------------ arguments of the replicate analyses
     @staticmethod
     def _weights(weights):

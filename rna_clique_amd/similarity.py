@@ -360,6 +360,15 @@ class SampleSimilarity:
         return pd.DataFrame({"component": comp, "sample": [self.labels[i] for i in s.ravel().tolist()],
                              "gene": g.ravel().astype(np.int64)}, columns=["component", "sample", "gene"])
 
+    def components(self):
+        """The census of every connected component of the graph, ideal or not
+        (census.ComponentTable): sizes, edge and sample counts, members, the
+        reference's plot_component_sizes statistics and histograms. Its
+        component numbering covers all components; the ideal ones keep the
+        relative order of ideal_components()."""
+        from .census import ComponentTable
+        return ComponentTable.from_engine(self.engine)
+
     def component_sums(self):
         """(num, den) int64 (C, P): every ideal component's share of each
         pair's restricted sums (pairs in engine.pair_order() numbering); a
