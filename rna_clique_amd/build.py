@@ -7,8 +7,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librcgpu.so")
-SOURCES = ["kernels.hip", "components.hip", "nj.hip", "pcoa.hip", "sort.hip", "align.hip", "dust.hip", "engine.hip", "results.hip",
-           "analysis.hip", "fasta.cpp", "graph_pickle.cpp", "od2_tables.cpp"]
+SOURCES = ["kernels.hip", "components.hip", "nj.hip", "pcoa.hip", "sort.hip", "seed.hip", "align.hip", "dust.hip",
+           "engine.hip", "results.hip", "analysis.hip", "fasta.cpp", "graph_pickle.cpp", "od2_tables.cpp"]
 HEADERS = ["device.h", "launch.h", "engine.h", "fail.h", "graph_pickle.h",
            os.path.join("..", "..", "include", "rcgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

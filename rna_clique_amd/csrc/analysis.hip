@@ -317,7 +317,7 @@ int rc_resample(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n
     }
     HIPCHK(hipStreamSynchronize(e->st));
     e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
-    if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    if (status & ST_NO_IDEAL) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;
 }
 

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void resample_kernel(const uint2 *__
 }
 
 // distance_kernel's formula over R replicates: out[r][i][j] for order[M],
-// 0 on the diagonal, NaN and status bit 4 where a denominator is 0
+// 0 on the diagonal, NaN and ST_NO_IDEAL where a denominator is 0
 __global__ void resample_distance_kernel(const ull *__restrict__ num, const ull *__restrict__ den,
                                          const int32_t *__restrict__ pair_index, const int32_t *__restrict__ order,
                                          int N, int M, uint64_t R, uint64_t P, double *__restrict__ out,
@@ -207,7 +207,7 @@ __global__ void resample_distance_kernel(const ull *__restrict__ num, const ull 
         }
         out[t] = d;
     }
-    if (__any(nan) && (threadIdx.x & 63) == 0) atomicOr(status, 4u);
+    if (__any(nan) && (threadIdx.x & 63) == 0) atomicOr(status, ST_NO_IDEAL);
 }
 
 // ------------------------------------------------------------------------

@@ -14,6 +14,17 @@ constexpr int ISO_LDS = 128;    // a gene's isoform tables the seed kernel keeps
 constexpr uint64_t MAX_TX = 1ull << 27;   // transcripts per engine (27-bit field of the seed key)
 constexpr int MAX_SAMPLES = 65535;         // samples per engine (16-bit fields of Cand and the big-pass list)
 
+// Bits of the engine's status word (d_status[0]): kernels raise them with
+// atomicOr, the host reads the word back after the stage.
+enum StatusBit : unsigned int {
+    ST_OVERFLOW = 1,        // a buffer overflowed, retry with larger ones: the seed or candidate buffers
+                            // (seed stage), the HSP overflow buffer (extension)
+    ST_GENE_LIMIT = 2,      // a gene has more isoforms than max_iso
+    ST_NO_IDEAL = 4,        // a pair without ideal rows, or NaN (distance kernels)
+    ST_BIG_LIST_FULL = 8,   // the big-pass list overflowed
+    ST_SEED_INDEX = 16,     // a first seed past 65534 (the record's 16 bits)
+};
+
 // Transcript record (16 B, one load).
 struct TxInfo {
     uint64_t start;   // global base offset of the transcript
@@ -239,7 +250,7 @@ struct SeedParams {
     unsigned long long *cand_count;  // [NSHARD]
     uint32_t *gc_off, *gc_cnt;    // [(g - gene_begin) * N + T] candidates of (gene, sample)
     const uint64_t *tmask;        // [n_samples][tmw] subject samples (> query sample) of this shard
-    unsigned int *status;         // bit 0 overflow, bit 1 gene limit, bit 3 big list full, bit 4 seed index > 16 bits
+    unsigned int *status;         // ST_OVERFLOW, ST_GENE_LIMIT, ST_BIG_LIST_FULL, ST_SEED_INDEX
     unsigned long long *prof;     // RC_ROW_TIMING builds: block cycles per phase
     // (gene, sample) passes whose seeds overflow LDS: ((gene - gene_begin) << 16) | sample
     uint64_t *big_out;            // the LDS kernel appends here
@@ -315,7 +326,7 @@ struct ExtParams {
     DHsp *ovf;
     uint64_t ovf_cap;
     unsigned long long *ovf_count;
-    unsigned int *status;         // bit 0 overflow
+    unsigned int *status;         // ST_OVERFLOW
     unsigned long long *counters; // d_count + DC_COUNTERS: counters[DC_x - DC_COUNTERS] (one atomic per wave);
                                   // null: a retry, whose work the first attempt counted
     // row kernels: staging slot (u64 words per sequence); win: the slot is
@@ -410,8 +421,10 @@ struct LaterParams {
 // passes the mirrored direction's) and its index in the candidate (bits 3-5).
 constexpr int HSP_FWD = 2, HSP_REV = 4, HSP_IDX_SHIFT = 3;
 
-// cand_box record: BOX_REC ints per candidate (align.hip FX_*)
+// cand_box record of a first-seed extension, BOX_REC ints per candidate:
+// status (0 done, -1 deferred), right (score, i, j, d, gap state), left (same)
 constexpr int BOX_REC = 12;
+enum { FX_STATUS = 0, FX_R = 1, FX_L = 6 };
 
 
 // group kernels: candidates of each (gene, sample) -> contiguous HSP groups.

@@ -1126,7 +1126,7 @@ static int reverse_pass(rc_engine *e, int ti, const Db &db, const Index &ixm, ui
         HIPCHK(hipMemcpyAsync(&cnt, e->work.d_rctr.p + 1, sizeof cnt, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
-        if (status & 2u)
+        if (status & ST_GENE_LIMIT)
             return fail(RC_E_LIMIT, "a query gene has more than " + std::to_string(max_iso(e->xbits)) + " isoforms");
         if (cnt <= e->rseed_cap) break;
         e->rseed_cap = cnt + cnt / 4 + 1024;
@@ -1452,9 +1452,9 @@ static int seed_big_passes(rc_engine *e, const TileCtx &C, const SeedParams &S, 
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(&nr, big_retry_n, sizeof nr, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
-        if (status & 16u)
+        if (status & ST_SEED_INDEX)
             return fail(RC_E_LIMIT, "a candidate's first seed of a directed search is past seed 65534");
-        again = (status & 1u) != 0;
+        again = (status & ST_OVERFLOW) != 0;
         nb = nr;
         // the retry entries become the next list (buffers swapped, not copied)
         e->work.d_big_list.swap(e->work.d_big_retry);
@@ -1544,16 +1544,16 @@ static int seed_stage(rc_engine *e, TileCtx &C)
             HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
             HIPCHK(hipMemcpyAsync(&nb, big_n, sizeof nb, hipMemcpyDeviceToHost, e->st));
             CHK(wait_st(e));
-            if (status & 2u)
+            if (status & ST_GENE_LIMIT)
                 return fail(RC_E_LIMIT, "a query gene has more than " + std::to_string(max_iso(e->xbits)) + " isoforms");
-            if (status & 16u)
+            if (status & ST_SEED_INDEX)
                 return fail(RC_E_LIMIT, "a candidate's first seed of a directed search is past seed 65534");
-            if (status & 8u) {   // the big-pass list itself overflowed
+            if (status & ST_BIG_LIST_FULL) {   // the big-pass list itself overflowed
                 e->big_list_cap = std::max<uint64_t>(4 * e->big_list_cap, nb + 1024);
                 again = true;
                 break;
             }
-            again = (status & 1u) != 0;
+            again = (status & ST_OVERFLOW) != 0;
             n_big += nb;
             CHK(seed_big_passes(e, C, S, nb, again));
         }
@@ -1826,7 +1826,7 @@ static int extension_stage(rc_engine *e, TileCtx &C)
         HIPCHK(hipMemcpyAsync(&status, e->d_status.p, sizeof status, hipMemcpyDeviceToHost, e->st));
         CHK(wait_st(e));
         if (c(DC_T_TRANS) || c(DC_T_STEPS)) CHK(print_row_timing(e, ctr));   // built with RC_ROW_TIMING
-        if (!(status & 1u)) {
+        if (!(status & ST_OVERFLOW)) {
             e->tm.ext_steps += c(DC_STEPS);
             e->tm.ext_calls += c(DC_EXTS);
             e->tm.ext_fullband += c(DC_FULLBAND);
@@ -1899,7 +1899,7 @@ static int group_stage(rc_engine *e, const TileCtx &C)
     for (size_t r = 0; r < R; r++) {
         const size_t nsgrp = cnb[r + 1] - cnb[r] - 1;
         HIPCHK(hipMemsetAsync(e->work.d_gcount.p + cnb[r] + nsgrp, 0, 4, e->st));
-        launch_group(run_group(r), 0, e->st);
+        launch_group(run_group(r), GROUP_DIRECT_COUNT, e->st);
         CHK(exscan(e->work.d_gcount.p + cnb[r], e->work.d_gscan.p + cnb[r], nsgrp + 1));
         HIPCHK(hipMemcpyAsync(&nd[r], e->work.d_gscan.p + cnb[r] + nsgrp, 8, hipMemcpyDeviceToHost, e->st));
     }
@@ -1935,7 +1935,7 @@ static int group_stage(rc_engine *e, const TileCtx &C)
         G.mcnt = e->work.d_mcnt.p;
         G.mcur = e->work.d_mcur.p;
         HIPCHK(hipMemsetAsync(e->work.d_mcnt.p, 0, (nwin + 1) * 4, e->st));
-        launch_group(G, 2, e->st);   // mirrored groups (spec 5b)
+        launch_group(G, GROUP_MIRROR_COUNT, e->st);   // mirrored groups (spec 5b)
         CHK(exscan(e->work.d_mcnt.p, e->work.d_mscan.p, nwin + 1));
         HIPCHK(hipMemcpyAsync(&nm, e->work.d_mscan.p + nwin, 8, hipMemcpyDeviceToHost, e->st));
     }
@@ -1953,7 +1953,7 @@ static int group_stage(rc_engine *e, const TileCtx &C)
         g.cand_ovf = e->work.d_cand_ovf.p;
         g.out = e->d_hsp.p;
         g.base = base;
-        launch_group(g, 1, e->st);
+        launch_group(g, GROUP_DIRECT_WRITE, e->st);
         base += nd[r];
     }
     if (mirror) {
@@ -1966,8 +1966,8 @@ static int group_stage(rc_engine *e, const TileCtx &C)
         G.mkey = e->work.d_mkey.p;
         G.mbig = e->work.d_mbig.p;
         G.mbig_n = e->d_count.p + DC_MBIG;
-        launch_group(G, 3, e->st);
-        launch_group(G, 4, e->st);
+        launch_group(G, GROUP_MIRROR_SCATTER, e->st);
+        launch_group(G, GROUP_MIRROR_SORT, e->st);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[EV_GROUPS1], e->st));

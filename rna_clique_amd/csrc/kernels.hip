@@ -709,7 +709,7 @@ __global__ void distance_kernel(const unsigned long long *num, const unsigned lo
     const unsigned long long dn = den[p], nm = num[p];
     if (dn == 0) {
         out[t] = __builtin_nan("");
-        atomicOr(status, 4u);
+        atomicOr(status, ST_NO_IDEAL);
         return;
     }
     out[t] = (double)(long long)(dn - nm) / (double)(long long)dn;

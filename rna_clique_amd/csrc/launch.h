@@ -1,8 +1,8 @@
 // The host entry points of the kernel files: every non-static host function
-// that kernels.hip, components.hip, nj.hip, pcoa.hip, sort.hip, align.hip and dust.hip
-// define, declared here and nowhere else. The defining files include this
-// header too, so a definition whose return type drifts from its declaration
-// does not compile.
+// that kernels.hip, components.hip, nj.hip, pcoa.hip, sort.hip, seed.hip, align.hip
+// and dust.hip define, declared here and nowhere else. The defining files
+// include this header too, so a definition whose return type drifts from its
+// declaration does not compile.
 #pragma once
 #include "device.h"
 
@@ -87,17 +87,19 @@ int os_index_sort(uint64_t *keys, uint64_t *alt, uint64_t n, int G, int bits, ui
                   uint64_t *status, uint32_t &epoch, uint32_t *offsets, uint32_t *list, uint32_t *bucket,
                   hipStream_t st, bool counted, const std::function<bool()> &wait, uint32_t *fb_ranges,
                   uint64_t *fb_keys, bool *whole);
-// align.hip
+// seed.hip
 void launch_seed(bool, const Db &, const Index &, const SeedParams &, hipStream_t);
 void launch_seed_big(bool, const Db &, const Index &, const SeedParams &, uint32_t, hipStream_t);
 void launch_rs_range(const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
+// align.hip
 void launch_extend_rows(bool, const Db &, const ExtParams &, hipStream_t);
 void launch_extend_retry(bool, const Db &, const ExtParams &, hipStream_t);
 void launch_later_rounds(bool, const Db &, const ExtParams &, bool, const LaterParams &, Cand *const[2],
                          uint32_t *const[2], int32_t *const[2], uint32_t *const[2], unsigned long long *, hipStream_t);
 void launch_later_finish(const ExtParams &, const LaterParams &, hipStream_t);
 int row_slot_words_max(bool amb);
-void launch_group(const GroupParams &, int, hipStream_t);
+enum GroupPass { GROUP_DIRECT_COUNT, GROUP_DIRECT_WRITE, GROUP_MIRROR_COUNT, GROUP_MIRROR_SCATTER, GROUP_MIRROR_SORT };
+void launch_group(const GroupParams &, GroupPass, hipStream_t);
 // dust.hip
 void launch_dust(bool, uint64_t, uint64_t, const uint64_t *, const uint64_t *, const uint64_t *, const TxInfo *, uint32_t, int,
                  int, int, uint32_t *, uint64_t *, uint32_t, uint64_t *, hipStream_t);

@@ -344,7 +344,7 @@ int rc_distance_subset(rc_engine *e, const int32_t *order, int32_t n, double *ou
     HIPCHK(hipMemcpyAsync(out, e->d_dist.p, (size_t)n * n * 8, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipMemcpyAsync(&status, e->d_status.p, 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
-    if (status & 4u) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    if (status & ST_NO_IDEAL) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;
 }
 

@@ -1,6 +1,7 @@
-"""The alignment kernels (align.hip: the seed kernel, the 32- and 64-lane row
-kernels, first_finish_kernel, the later-seed rounds, extend_kernel) on the
-hand-built cases of tests/align_cases.py, against the C oracle bit for bit.
+"""The alignment kernels (seed.hip: the seed kernel; align.hip: the 32- and
+64-lane row kernels, first_finish_kernel, the later-seed rounds,
+extend_kernel) on the hand-built cases of tests/align_cases.py, against the C
+oracle bit for bit.
 
 tests/test_align_cases_host.py shows on the CPU which edge of the spec each
 case lands on (the band's two edges, the 32-lane window, the X-drop
