@@ -1,6 +1,7 @@
 // The host entry points of the kernel files: every non-static host function
-// that kernels.hip, components.hip, nj.hip, pcoa.hip, sort.hip, seed.hip, align.hip
-// and dust.hip define, declared here and nowhere else. The defining files
+// that kernels.hip, components.hip, nj.hip, pcoa.hip, sort.hip, seed.hip,
+// align.hip, rows.hip, finish.hip, extend.hip, group.hip and dust.hip define,
+// one section per unit, declared here and nowhere else. The defining files
 // include this header too, so a definition whose return type drifts from its
 // declaration does not compile.
 #pragma once
@@ -91,13 +92,20 @@ int os_index_sort(uint64_t *keys, uint64_t *alt, uint64_t n, int G, int bits, ui
 void launch_seed(bool, const Db &, const Index &, const SeedParams &, hipStream_t);
 void launch_seed_big(bool, const Db &, const Index &, const SeedParams &, uint32_t, hipStream_t);
 void launch_rs_range(const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
-// align.hip
+// align.hip (the pass order of the extension, over the four units below)
 void launch_extend_rows(bool, const Db &, const ExtParams &, hipStream_t);
-void launch_extend_retry(bool, const Db &, const ExtParams &, hipStream_t);
 void launch_later_rounds(bool, const Db &, const ExtParams &, bool, const LaterParams &, Cand *const[2],
                          uint32_t *const[2], int32_t *const[2], uint32_t *const[2], unsigned long long *, hipStream_t);
-void launch_later_finish(const ExtParams &, const LaterParams &, hipStream_t);
+// rows.hip
+void launch_rows(int rw, bool save, bool amb, const Db &, const ExtParams &, hipStream_t);
 int row_slot_words_max(bool amb);
+// finish.hip
+void launch_first_finish(const ExtParams &, hipStream_t);
+void launch_later_round(const ExtParams &, const LaterParams &, hipStream_t);
+void launch_later_finish(const ExtParams &, const LaterParams &, hipStream_t);
+// extend.hip
+void launch_extend_retry(bool, const Db &, const ExtParams &, hipStream_t);
+// group.hip
 enum GroupPass { GROUP_DIRECT_COUNT, GROUP_DIRECT_WRITE, GROUP_MIRROR_COUNT, GROUP_MIRROR_SCATTER, GROUP_MIRROR_SORT };
 void launch_group(const GroupParams &, GroupPass, hipStream_t);
 // dust.hip

@@ -1,7 +1,7 @@
-"""The alignment kernels (seed.hip: the seed kernel; align.hip: the 32- and
-64-lane row kernels, first_finish_kernel, the later-seed rounds,
-extend_kernel) on the hand-built cases of tests/align_cases.py, against the C
-oracle bit for bit.
+"""The alignment kernels (seed.hip: the seed kernel; rows.hip: the 32- and
+64-lane row kernels; finish.hip: first_finish_kernel, the later-seed rounds;
+extend.hip: extend_kernel; align.hip: the order of their passes) on the
+hand-built cases of tests/align_cases.py, against the C oracle bit for bit.
 
 tests/test_align_cases_host.py shows on the CPU which edge of the spec each
 case lands on (the band's two edges, the 32-lane window, the X-drop

@@ -369,3 +369,21 @@ def test_pytables_branch_is_serialised(tmp_path, monkeypatch):
         list(ex.map(lambda i: write_table(df, tmp_path / f"t{i}.h5"), range(6)))
     assert state["calls"] == 6
     assert state["max"] == 1
+
+
+def test_build_lists_name_every_source_and_header():
+    """build.SOURCES is every *.hip and *.cpp of csrc/, and build.HEADERS
+    every header an #include "..." of csrc/ names (paths relative to csrc/,
+    normalised). A unit missing from SOURCES shows up only as an undefined
+    symbol when the library is loaded; a header missing from HEADERS is not
+    seen by the staleness check."""
+    from rna_clique_amd import build
+    files = sorted(os.listdir(build.CSRC))
+    assert {f for f in files if f.endswith((".hip", ".cpp"))} == set(build.SOURCES)
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    included = set()
+    for f in files:
+        with open(os.path.join(build.CSRC, f)) as src:
+            included |= {os.path.normpath(m) for m in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src.read(), re.M)}
+    assert included
+    assert included <= {os.path.normpath(h) for h in build.HEADERS}
