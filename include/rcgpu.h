@@ -48,6 +48,8 @@ extern "C" {
  *   bases per alignment tile      2^32 (a shard is cut into tiles below that)
  *   seeds per (query gene, subject sample) pass 2^22
  *   samples in a neighbour-joining tree 1024 (rc_nj, rc_resample_trees)
+ *   splits in a census            2^31 - 1 (rc_split_census, rc_tree_rf)
+ *   trees in a pairwise distance matrix 8192 (rc_tree_rf)
  *   samples in a principal coordinates analysis 128 (rc_pcoa, rc_resample_pcoa) */
 #define RC_E_IO (-8)         /* file could not be written */
 
@@ -165,6 +167,9 @@ typedef struct rc_timing {
                                  (uploads and the copies back are outside it) */
     double pcoa_ms;           /* device time of the last rc_pcoa / rc_resample_pcoa's eigensolver kernel
                                  (uploads and the copies back are outside it) */
+    double split_ms;          /* device time of the kernels that the last rc_split_census / rc_tree_rf ran: the
+                                 census when that call built it, the gather of the distinct splits, the
+                                 distances (the copies back are outside it) */
 } rc_timing;
 
 void rc_default_opts(rc_opts *opts);
@@ -385,6 +390,40 @@ int rc_nj(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, int32_t *jo
 int rc_resample_trees(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
                       int32_t n, int32_t *joins, double *lengths, uint64_t *splits, uint8_t *valid,
                       const uint64_t *ref_splits, int32_t n_ref, uint32_t *support, uint32_t *n_valid);
+
+/* ---- split census and Robinson-Foulds distances of replicate trees ---------
+ * Both calls analyse the trees that the last rc_nj / rc_resample_trees of this
+ * engine left on the device (n_rep trees of n samples, ns = n - 3 splits each
+ * in W words); RC_E_STATE before the first of them. An instance is (replicate
+ * r, join t) with flat index r * ns + t; only valid replicates count. The
+ * census numbers the distinct splits 0..K-1 in ascending order of their first
+ * instance's flat index, which does not depend on the order in which the
+ * device's atomics land: two calls return identical bytes. It is built by the
+ * first of these calls after the trees (a hash table of 8 to 16 bytes and 8
+ * more bytes per instance stay on the device) and dropped by the next rc_nj /
+ * rc_resample_trees. rc_trim frees none of the tree buffers, so the census
+ * survives it. RC_E_LIMIT: n_rep * ns >= 2^31.
+ *
+ * rc_split_census: splits[k] the W words of split k, count[k] the number of
+ * valid replicates that have it, ids[r * ns + t] the number of the split of
+ * join t of replicate r (-1 in an invalid replicate; NULL: not wanted),
+ * n_valid the number of valid replicates (may be NULL). splits == count ==
+ * NULL queries n_distinct; one of the two NULL is RC_E_ARG; cap < n_distinct
+ * is RC_E_CAPACITY (n_distinct is set). With n == 3, n_distinct is 0.
+ *
+ * rc_tree_rf: Robinson-Foulds distances, the size of the symmetric difference
+ * of two trees' split sets. to_ref[r] = n_ref + ns - 2 |splits(r) & ref| for
+ * the n_ref distinct reference splits ref_splits (n_ref x W words, checked as
+ * rc_nj checks them); pairwise[a * n_rep + b] = 2 ns - 2 |splits(a) &
+ * splits(b)|, symmetric with a zero diagonal. Entries of an invalid replicate
+ * are 0xFFFFFFFF in both arrays, row and column. Either output may be NULL.
+ * RC_E_ARG: to_ref without ref_splits, n_ref < 0, a bad reference split.
+ * RC_E_LIMIT: pairwise with n_rep > 8192 (a result of 256 MB). */
+int rc_split_census(rc_engine *eng, uint64_t *splits /* cap x W */, uint32_t *count /* cap */,
+                    int32_t *ids /* n_rep x (n-3), or NULL */, uint64_t cap, uint64_t *n_distinct,
+                    uint32_t *n_valid);
+int rc_tree_rf(rc_engine *eng, const uint64_t *ref_splits, int32_t n_ref, uint32_t *to_ref /* n_rep or NULL */,
+               uint32_t *pairwise /* n_rep x n_rep or NULL */);
 
 /* ---- principal coordinates (PCoA, classical scaling) -----------------------
  * The eigenvalues and eigenvectors of the Gower-centred matrix of every

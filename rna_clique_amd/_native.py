@@ -89,7 +89,7 @@ class RcTiming(ctypes.Structure):
         "band_bound", "maxhsp_bound", "ext_second", "near_index", "reverse_seeds", "ext_slides", "ext_wide", "dev_bytes",
         "dev_peak_bytes", "defer_length", "defer_gaveup", "defer_outside", "index_reused",
         "ext_retries", "load_ms", "align_wall_ms", "host_wait_ms", "later_seeds", "later_whole",
-        "index_fb_ranges", "index_fb_keys", "resample_ms", "nj_ms", "pcoa_ms")]
+        "index_fb_ranges", "index_fb_keys", "resample_ms", "nj_ms", "pcoa_ms", "split_ms")]
 
 
 assert HSP_DTYPE.itemsize == ctypes.sizeof(RcHsp)
@@ -142,6 +142,8 @@ SIGNATURES = {
     "rc_nj": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int32, VP, VP, VP, VP, VP, ctypes.c_int32, VP, VP]),
     "rc_resample_trees": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, VP, VP, VP, VP,
                                          VP, ctypes.c_int32, VP, VP]),
+    "rc_split_census": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint32)]),
+    "rc_tree_rf": (ctypes.c_int, [VP, VP, ctypes.c_int32, VP, VP]),
     "rc_pcoa": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, VP, VP, VP]),
     "rc_resample_pcoa": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_int32, VP, VP, VP, VP]),

@@ -1,6 +1,6 @@
 // Analyses of a finished engine's graph: per-component tables, bootstrap
-// resampling, neighbour-joining trees and principal coordinates (kernels:
-// components.hip, nj.hip, pcoa.hip).
+// resampling, neighbour-joining trees, the census of their splits and
+// principal coordinates (kernels: components.hip, nj.hip, splits.hip, pcoa.hip).
 #include "engine.h"
 
 // ------------------------------------------------------------------------
@@ -356,6 +356,8 @@ static int nj_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, i
 {
     const int W = (n + 63) / 64;
     const size_t R = (size_t)n_rep, nj = R * (size_t)(n - 2) * 3, ns = R * (size_t)(n - 3) * W;
+    e->an.nj_n = 0;   // the trees on the device go, and the census of their splits with them
+    e->an.split_valid = false;
     CHK(e->an.d_nj_joins.ensure(nj));
     CHK(e->an.d_nj_len.ensure(nj));
     CHK(e->an.d_nj_splits.ensure(ns));
@@ -397,6 +399,9 @@ static int nj_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, i
     HIPCHK(hipMemcpyAsync(&nv, e->an.d_nj_sup.p + n_ref, 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
     e->tm.nj_ms = ev_ms(e, EV_NJ0, EV_NJ1);
+    e->an.nj_rep = n_rep;
+    e->an.nj_n = n;
+    e->an.nj_nvalid = nv;
     if (n_valid) *n_valid = nv;
     *invalid = (uint32_t)n_rep - nv;
     return RC_OK;
@@ -433,6 +438,142 @@ int rc_resample_trees(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint
                   &invalid));
     e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
     if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    return RC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// split census and Robinson-Foulds distances (splits.hip)
+// ------------------------------------------------------------------------
+
+static const int32_t RF_MAX_PAIRWISE = 8192;   // replicates of a pairwise matrix (256 MB)
+
+// The census of the splits that the last nj_device left in d_nj_splits /
+// d_nj_valid, built once per batch of trees: the hash table, the rank and the
+// class id of every instance, count and first instance of every class. It
+// stays on the device until the next nj_device.
+static int build_splits(rc_engine *e)
+{
+    rc_engine::Analysis &a = e->an;
+    if (!a.nj_n) return fail(RC_E_STATE, "no trees on this engine yet (rc_nj, rc_resample_trees)");
+    CHK(set_device(e));
+    if (a.split_valid) return RC_OK;
+    const uint64_t ns = (uint64_t)(a.nj_n - 3), ni = (uint64_t)a.nj_rep * ns;
+    if (ni >> 31) return fail(RC_E_LIMIT, "2^31 or more splits in the replicate trees");
+    const int W = (a.nj_n + 63) / 64;
+    uint64_t K = 0, slots = 0;
+    DBuf<uint32_t> rep, flag;
+    CHK(a.d_sp_ids.ensure(ni));
+    CHK(a.d_sp_rank.ensure(ni));
+    if (ni) {
+        slots = split_table_slots(ni);
+        CHK(a.d_sp_table.ensure(slots));
+        CHK(rep.ensure(ni));
+        CHK(flag.ensure(ni));
+        HIPCHK(hipMemsetAsync(a.d_sp_table.p, 0xFF, slots * 4, e->st));
+        launch_split_insert(a.d_nj_splits.p, a.d_nj_valid.p, (uint32_t)ni, (uint32_t)ns, W, a.d_sp_table.p, slots, e->st);
+        launch_split_lookup(a.d_nj_splits.p, a.d_nj_valid.p, (uint32_t)ni, (uint32_t)ns, W, a.d_sp_table.p, slots, rep.p,
+                            flag.p, e->st);
+        HIPCHK(hipGetLastError());
+        size_t tmp = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, flag.p, a.d_sp_rank.p, 0u, (size_t)ni, rocprim::plus<uint32_t>(),
+                                       e->st));
+        CHK(e->work.d_tmp.ensure(tmp));
+        HIPCHK(rocprim::exclusive_scan(e->work.d_tmp.p, tmp, flag.p, a.d_sp_rank.p, 0u, (size_t)ni,
+                                       rocprim::plus<uint32_t>(), e->st));
+        uint32_t last_rank = 0, last_flag = 0;
+        HIPCHK(hipMemcpyAsync(&last_rank, a.d_sp_rank.p + ni - 1, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(&last_flag, flag.p + ni - 1, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipStreamSynchronize(e->st));
+        K = (uint64_t)last_rank + last_flag;
+    }
+    CHK(a.d_sp_count.ensure(K));
+    CHK(a.d_sp_first.ensure(K));
+    if (K) {
+        HIPCHK(hipMemsetAsync(a.d_sp_count.p, 0, K * 4, e->st));
+        launch_split_ids(rep.p, a.d_sp_rank.p, (uint32_t)ni, a.d_sp_ids.p, a.d_sp_count.p, a.d_sp_first.p, e->st);
+        HIPCHK(hipGetLastError());
+    } else if (ni) {
+        HIPCHK(hipMemsetAsync(a.d_sp_ids.p, 0xFF, ni * 4, e->st));   // no valid replicate: every id -1
+    }
+    HIPCHK(hipStreamSynchronize(e->st));   // rep, flag go out of scope
+    a.split_K = K;
+    a.split_slots = slots;
+    a.split_valid = true;
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_split_census(rc_engine *e, uint64_t *splits, uint32_t *count, int32_t *ids, uint64_t cap, uint64_t *n_distinct,
+                    uint32_t *n_valid)
+{
+    if (!e || !n_distinct) return fail(RC_E_ARG, "null argument");
+    rc_engine::Analysis &a = e->an;
+    if (!a.nj_n) return fail(RC_E_STATE, "no trees on this engine yet (rc_nj, rc_resample_trees)");
+    CHK(set_device(e));
+    HIPCHK(hipEventRecord(e->ev[EV_SPLIT0], e->st));
+    CHK(build_splits(e));
+    const uint64_t K = a.split_K, ni = (uint64_t)a.nj_rep * (uint64_t)(a.nj_n - 3);
+    const int W = (a.nj_n + 63) / 64;
+    *n_distinct = K;
+    if (n_valid) *n_valid = a.nj_nvalid;
+    if ((splits == nullptr) != (count == nullptr)) return fail(RC_E_ARG, "splits and count go together");
+    if (splits && cap < K) return fail(RC_E_CAPACITY, "buffer too small");
+    if (splits && K) {
+        CHK(a.d_sp_out.ensure(K * W));
+        launch_split_gather(a.d_nj_splits.p, a.d_sp_first.p, K, W, a.d_sp_out.p, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->ev[EV_SPLIT1], e->st));
+    if (splits && K) {
+        HIPCHK(hipMemcpyAsync(splits, a.d_sp_out.p, K * W * 8, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(hipMemcpyAsync(count, a.d_sp_count.p, K * 4, hipMemcpyDeviceToHost, e->st));
+    }
+    if (ids && ni) HIPCHK(hipMemcpyAsync(ids, a.d_sp_ids.p, ni * 4, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.split_ms = ev_ms(e, EV_SPLIT0, EV_SPLIT1);
+    return RC_OK;
+}
+
+int rc_tree_rf(rc_engine *e, const uint64_t *ref_splits, int32_t n_ref, uint32_t *to_ref, uint32_t *pairwise)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    rc_engine::Analysis &a = e->an;
+    if (!a.nj_n) return fail(RC_E_STATE, "no trees on this engine yet (rc_nj, rc_resample_trees)");
+    if (to_ref && !ref_splits) return fail(RC_E_ARG, "to_ref needs ref_splits");
+    CHK(nj_check(a.nj_rep, a.nj_n, ref_splits, n_ref, nullptr));
+    if (pairwise && a.nj_rep > RF_MAX_PAIRWISE)
+        return fail(RC_E_LIMIT, "a pairwise distance matrix of more than 8192 replicates");
+    CHK(set_device(e));
+    HIPCHK(hipEventRecord(e->ev[EV_SPLIT0], e->st));
+    CHK(build_splits(e));
+    const uint32_t R = (uint32_t)a.nj_rep, ns = (uint32_t)(a.nj_n - 3);
+    const int W = (a.nj_n + 63) / 64;
+    if (to_ref) {
+        CHK(a.d_nj_ref.ensure((size_t)n_ref * W));
+        CHK(a.d_sp_isref.ensure(a.split_K));
+        CHK(a.d_rf_ref.ensure(R));
+        if (a.split_K) HIPCHK(hipMemsetAsync(a.d_sp_isref.p, 0, a.split_K, e->st));
+        if (n_ref && a.split_K) {
+            HIPCHK(hipMemcpyAsync(a.d_nj_ref.p, ref_splits, (size_t)n_ref * W * 8, hipMemcpyHostToDevice, e->st));
+            launch_split_ref(a.d_nj_ref.p, n_ref, a.d_nj_splits.p, W, a.d_sp_table.p, a.split_slots, a.d_sp_rank.p,
+                             a.d_sp_isref.p, e->st);
+        }
+        launch_rf_ref(a.d_sp_ids.p, a.d_nj_valid.p, a.d_sp_isref.p, R, ns, (uint32_t)n_ref, a.d_rf_ref.p, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    if (pairwise) {
+        CHK(a.d_rf_pair.ensure((size_t)R * R));
+        launch_rf_pairs(a.d_sp_ids.p, a.d_nj_valid.p, R, ns, a.d_rf_pair.p, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->ev[EV_SPLIT1], e->st));
+    if (to_ref) HIPCHK(hipMemcpyAsync(to_ref, a.d_rf_ref.p, (size_t)R * 4, hipMemcpyDeviceToHost, e->st));
+    if (pairwise) HIPCHK(hipMemcpyAsync(pairwise, a.d_rf_pair.p, (size_t)R * R * 4, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.split_ms = ev_ms(e, EV_SPLIT0, EV_SPLIT1);
     return RC_OK;
 }
 

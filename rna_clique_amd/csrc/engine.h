@@ -188,6 +188,7 @@ enum Ev {
     EV_RESAMPLE0 = 12, EV_RESAMPLE1 = 13,   // resample_fill: the replicate sums (resample_ms)
     EV_NJ0 = 14, EV_NJ1 = 15,               // nj_device: the trees and the split support (nj_ms)
     EV_PCOA0 = 16, EV_PCOA1 = 17,           // pcoa_device: the ordinations (pcoa_ms)
+    EV_SPLIT0 = 18, EV_SPLIT1 = 19,         // rc_split_census, rc_tree_rf: the census and RF kernels (split_ms)
     EV_N
 };
 // rc_engine::evd: DUST on the second stream
@@ -391,6 +392,20 @@ struct rc_engine {
         DBuf<uint64_t> d_nj_splits, d_nj_ref, d_nj_wsmask;
         DBuf<uint8_t> d_nj_valid;
         DBuf<uint32_t> d_nj_sup;
+        // The trees that d_nj_splits / d_nj_valid hold (nj_device; nj_n == 0:
+        // none yet) and the census of their splits (splits.hip), built by the
+        // first rc_split_census / rc_tree_rf after them and dropped by the next
+        // nj_device: the hash table, per instance the rank of its flat index
+        // among the class representatives and its class id, per class the
+        // count and the first instance.
+        int32_t nj_rep = 0, nj_n = 0;
+        uint32_t nj_nvalid = 0;
+        bool split_valid = false;
+        uint64_t split_K = 0, split_slots = 0;
+        DBuf<uint32_t> d_sp_table, d_sp_rank, d_sp_count, d_sp_first, d_rf_ref, d_rf_pair;
+        DBuf<int32_t> d_sp_ids;
+        DBuf<uint64_t> d_sp_out;
+        DBuf<uint8_t> d_sp_isref;
         // principal coordinates (pcoa.hip): input matrices of rc_pcoa, the results
         // and the status words (invalid, unconverged replicates)
         DBuf<double> d_pcoa_in, d_pcoa_val, d_pcoa_vec;

@@ -1,6 +1,6 @@
 // The host entry points of the kernel files: every non-static host function
-// that kernels.hip, components.hip, nj.hip, pcoa.hip, sort.hip, seed.hip,
-// align.hip, rows.hip, finish.hip, extend.hip, group.hip and dust.hip define,
+// that kernels.hip, components.hip, nj.hip, splits.hip, pcoa.hip, sort.hip,
+// seed.hip, align.hip, rows.hip, finish.hip, extend.hip, group.hip and dust.hip define,
 // one section per unit, declared here and nowhere else. The defining files
 // include this header too, so a definition whose return type drifts from its
 // declaration does not compile.
@@ -61,6 +61,18 @@ hipError_t launch_nj(bool, const double *, int, int, int, double *, uint64_t *, 
                      uint8_t *, hipStream_t);
 void launch_nj_support(const uint64_t *, int, const uint64_t *, const uint8_t *, int, int, int, uint32_t *, uint32_t *,
                        hipStream_t);
+// splits.hip
+uint64_t split_table_slots(uint64_t);
+void launch_split_insert(const uint64_t *, const uint8_t *, uint32_t, uint32_t, int, uint32_t *, uint64_t, hipStream_t);
+void launch_split_lookup(const uint64_t *, const uint8_t *, uint32_t, uint32_t, int, const uint32_t *, uint64_t,
+                         uint32_t *, uint32_t *, hipStream_t);
+void launch_split_ids(const uint32_t *, const uint32_t *, uint32_t, int32_t *, uint32_t *, uint32_t *, hipStream_t);
+void launch_split_gather(const uint64_t *, const uint32_t *, uint64_t, int, uint64_t *, hipStream_t);
+void launch_split_ref(const uint64_t *, int, const uint64_t *, int, const uint32_t *, uint64_t, const uint32_t *,
+                      uint8_t *, hipStream_t);
+void launch_rf_ref(const int32_t *, const uint8_t *, const uint8_t *, uint32_t, uint32_t, uint32_t, uint32_t *,
+                   hipStream_t);
+void launch_rf_pairs(const int32_t *, const uint8_t *, uint32_t, uint32_t, uint32_t *, hipStream_t);
 // pcoa.hip
 int pcoa_ld(int);
 size_t pcoa_lds_bytes(int);

@@ -417,6 +417,8 @@ class Engine:
         ref, bufs = self._nj_buffers(r, m, ref_splits)
         nv = ctypes.c_uint32()
         code = nat.lib().rc_nj(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, *self._nj_args(ref, bufs, nv))
+        if code in (nat.RC_OK, nat.RC_E_NO_IDEAL):
+            self._trees = (r, m)   # the trees now on the device (split_census, tree_rf)
         if not (allow_nan and code == nat.RC_E_NO_IDEAL):
             nat.check(code)
         return NJResult(n_valid=nv.value, **bufs)
@@ -435,9 +437,59 @@ class Engine:
         vp = ctypes.c_void_p
         code = nat.lib().rc_resample_trees(self._h, w.ctypes.data_as(vp), r, w.shape[1], order.ctypes.data_as(vp), m,
                                            *self._nj_args(ref, bufs, nv))
+        if code in (nat.RC_OK, nat.RC_E_NO_IDEAL):
+            self._trees = (r, m)   # the trees now on the device (split_census, tree_rf)
         if not (allow_nan and code == nat.RC_E_NO_IDEAL):
             nat.check(code)
         return [self.labels[i] for i in order], NJResult(n_valid=nv.value, **bufs)
+
+    # ------------------------------------ split census and tree distances
+    def _tree_shape(self):
+        """(replicates, samples) of the trees on the device; without any, the
+        library's own error (RC_E_STATE)."""
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().rc_split_census(self._h, None, None, None, 0, ctypes.byref(n), None))
+        return self._trees
+
+    def split_census(self):
+        """The census of the splits of the last nj() / resample_trees() trees,
+        counted on the device (rc_split_census): tree.SplitCensus(splits (K, W)
+        uint64, counts (K,) uint32, ids (R, N-3) int32, n_valid). The distinct
+        splits are numbered in ascending order of their first occurrence
+        (replicate-major, then join order); counts[k] is the number of valid
+        trees that have split k; ids[r, t] is the number of split t of tree r,
+        -1 in an invalid tree."""
+        from .tree import SplitCensus, split_words
+        L = nat.lib()
+        r, m = self._tree_shape()
+        k, nv = ctypes.c_uint64(), ctypes.c_uint32()
+        nat.check(L.rc_split_census(self._h, None, None, None, 0, ctypes.byref(k), ctypes.byref(nv)))
+        splits = np.zeros((k.value, split_words(m)), dtype=np.uint64)
+        counts = np.zeros(k.value, dtype=np.uint32)
+        ids = np.zeros((r, m - 3), dtype=np.int32)
+        vp = ctypes.c_void_p
+        nat.check(L.rc_split_census(self._h, splits.ctypes.data_as(vp), counts.ctypes.data_as(vp),
+                                    ids.ctypes.data_as(vp), k.value, ctypes.byref(k), ctypes.byref(nv)))
+        return SplitCensus(splits, counts, ids, nv.value)
+
+    def tree_rf(self, ref_splits=None, pairwise=False):
+        """Robinson-Foulds distances of the last nj() / resample_trees() trees
+        (rc_tree_rf): (to_ref, pairwise). to_ref (R,) uint32: the distance of
+        every tree to the tree of the distinct splits `ref_splits` (n_ref, W)
+        uint64, None without them; pairwise (R, R) uint32 when asked for, else
+        None. Entries of an invalid tree are 0xFFFFFFFF."""
+        from .tree import split_words
+        r, m = self._tree_shape()
+        ref = to_ref = pw = None
+        if ref_splits is not None:
+            ref = np.ascontiguousarray(ref_splits, dtype=np.uint64).reshape(-1, split_words(m))
+            to_ref = np.zeros(r, dtype=np.uint32)
+        if pairwise:
+            pw = np.zeros((r, r), dtype=np.uint32)
+        vp = ctypes.c_void_p
+        ptr = lambda a: None if a is None else a.ctypes.data_as(vp)   # noqa: E731
+        nat.check(nat.lib().rc_tree_rf(self._h, ptr(ref), 0 if ref is None else len(ref), ptr(to_ref), ptr(pw)))
+        return to_ref, pw
 
     # ------------------------------------------------- principal coordinates
     @staticmethod

@@ -452,6 +452,50 @@ class SampleSimilarity:
         res = self._resample_trees(bootstrap_weights(self.engine.n_components(), n_rep, seed), tree.splits)
         return NJTree(tree.labels, tree.joins, tree.lengths, tree.splits, res.support / float(res.n_valid))
 
+    # ------------------------------- split census, consensus, tree distances
+    def _bootstrap_tree_weights(self, n_rep, seed):
+        """bootstrap_weights(C, n_rep, seed), the replicates of
+        bootstrap_support, with its errors."""
+        if len(self._order()) < 3:
+            raise ValueError("a tree needs at least 3 samples")
+        c = self.engine.n_components()
+        if c == 0:
+            raise NoIdealComponentsError()
+        return bootstrap_weights(c, n_rep, seed)
+
+    def resampled_split_census(self, weights):
+        """The census (tree.SplitCensus) of the splits of resampled_trees(
+        weights): every distinct split, the number of replicates that have it
+        and the split numbers of every replicate, counted on the GPU; the trees
+        do not leave it. Bit b of a split stands for self.samples[b]."""
+        self._resample_trees(weights)
+        return self.engine.split_census()
+
+    def bootstrap_split_census(self, n_rep, seed=0):
+        """resampled_split_census of bootstrap_support(n_rep, seed)'s
+        replicates: the count of a split of neighbor_joining_tree() is its
+        support there times n_valid."""
+        return self.resampled_split_census(self._bootstrap_tree_weights(n_rep, seed))
+
+    def bootstrap_consensus(self, n_rep, seed=0, method="majority", threshold=0.5):
+        """The consensus tree (tree.SplitTree) of bootstrap_support(n_rep,
+        seed)'s replicates: tree.consensus_tree with support and mean branch
+        lengths; method "strict", "majority" or "greedy"."""
+        from .tree import consensus_tree
+        res = self._resample_trees(self._bootstrap_tree_weights(n_rep, seed))
+        return consensus_tree(self.engine.split_census(), self.samples, res.lengths, res.joins, method, threshold)
+
+    def bootstrap_rf(self, n_rep, seed=0, pairwise=False):
+        """Robinson-Foulds distances of bootstrap_support(n_rep, seed)'s
+        replicates: (to_ref (n_rep,) uint32, the distance of each to
+        neighbor_joining_tree(); the (n_rep, n_rep) distances between them
+        when `pairwise`, else None). The scatter of the replicates in tree
+        space, as bootstrap_pcoa's spread is for the ordination."""
+        w = self._bootstrap_tree_weights(n_rep, seed)
+        tree = self.neighbor_joining_tree()
+        self._resample_trees(w)
+        return self.engine.tree_rf(tree.splits, pairwise)
+
     # ------------------------------------------- principal coordinates
     def _pcoa_order(self, dimensions, clip=False):
         """This object's sample order and the number of axes, checked; clip:
