@@ -18,17 +18,42 @@
 
 namespace rcg {
 
-constexpr int SBLOCK = 256;
+// Threads per query gene (one workgroup) and word items per round of the
+// lookup -> hits -> test chain. A C3 gene has ~146 word items, ~176 seeds and
+// ~16 candidates: most of 256 lanes idle in every phase, and what a CU can
+// hold is workgroups (registers, LDS), so smaller workgroups put more genes'
+// dependent chains in flight. Items per round are kept apart from the threads
+// (IPT items per thread, their loads in flight together) so that a typical
+// gene still takes one round. r19 (profiles/r19_seed_block, C3 seed kernel per
+// step, both passes): 256 threads at 5 workgroups per CU 65.8 ms; 128 threads
+// with 256 items per round at 8 per CU 56.5 (4 hits per lane 57.9); 128 items
+// per round at 8 per CU 58.8, at 10 per CU (96 VGPRs, 4 hits per lane) 57.3;
+// 64 threads at 8 per CU (two waves per SIMD) 65.6.
+#ifndef RC_SEED_BLOCK
+#define RC_SEED_BLOCK 128
+#endif
+#ifndef RC_SEED_ITEMS
+#define RC_SEED_ITEMS 256
+#endif
+constexpr int SBLOCK = RC_SEED_BLOCK;
+constexpr int SITEMS = RC_SEED_ITEMS;
+constexpr int IPT = SITEMS / SBLOCK;   // word items per thread per round
+static_assert(SBLOCK == 64 || SBLOCK == 128 || SBLOCK == 256, "RC_SEED_BLOCK: whole waves, a power of two (bitonic chunks)");
+static_assert(SITEMS % SBLOCK == 0 && SITEMS <= 256, "RC_SEED_ITEMS: a multiple of the block; item slots are 8-bit (hq_k)");
 // Seed kernel occupancy (r04, profiles/r04_i, C3 seed kernel per step):
 // 1024-seed LDS passes at 4 workgroups per CU 79.5 ms; 512-seed passes at 5
 // (96 VGPRs, 28 KB LDS) 70.7; 6 (2 hits per lane) 74.7; 256-seed passes at
 // 7 or 8: 92 / 98 (more passes halve their subject range). C3v: 103-104 ms
 // at 4 and 5 alike.
+// RC_SEED_WAVES and RC_SEED_REV_WAVES are the launch bound's waves per SIMD,
+// which the compiler lowers to what the LDS lets a CU hold: a CU holds
+// 4 x waves / (SBLOCK / 64) workgroups, so 4 waves of 128-thread workgroups
+// are 8 per CU (128 VGPRs, no scratch; 20.3 KB of LDS each: 8 need <= 20 480 B).
 #ifndef RC_SEED_CAP
 #define RC_SEED_CAP 512
 #endif
 #ifndef RC_SEED_WAVES
-#define RC_SEED_WAVES 5
+#define RC_SEED_WAVES (RC_SEED_BLOCK == 256 ? 5 : 4)
 #endif
 constexpr int SEED_CAP = RC_SEED_CAP;   // seeds of one pass in LDS (a power of two: the bitonic sort pads to one)
 static_assert((SEED_CAP & (SEED_CAP - 1)) == 0, "RC_SEED_CAP must be a power of two");
@@ -41,7 +66,8 @@ static_assert((SEED_CAP & (SEED_CAP - 1)) == 0, "RC_SEED_CAP must be a power of 
 constexpr int HBATCH = RC_HBATCH;
 // The reverse pass (REV) keeps no seeds in LDS and finds few hits (the
 // near-mask index is small): its own instantiation, without the seed and
-// per-sample arrays and with fewer hits per lane, runs more workgroups per CU.
+// per-sample arrays and with fewer hits per lane, runs more workgroups per CU
+// (7 waves per SIMD: 7 of 256 threads, 14 of 128).
 #ifndef RC_SEED_REV_WAVES
 #define RC_SEED_REV_WAVES 7
 #endif
@@ -73,7 +99,8 @@ __device__ __forceinline__ uint64_t qrev_pos(const QGeo &q, int strand, uint64_t
 // seeds
 // ------------------------------------------------------------------------
 
-// Exclusive scan of one value per thread over a SBLOCK-thread block.
+// Exclusive scan of one value per thread over a SBLOCK-thread block (wsum: a
+// slot per wave).
 __device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t *wsum, uint32_t &total)
 {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -97,10 +124,10 @@ __device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t *wsum, uin
     return before + x - v;
 }
 
-// last k with pre[k] <= h over an SBLOCK + 1 prefix table (the word a hit belongs to)
+// last k with pre[k] <= h over an SITEMS + 1 prefix table (the word a hit belongs to)
 __device__ __forceinline__ int run_of(const uint32_t *pre, uint32_t h)
 {
-    int lo = 0, hi = SBLOCK;
+    int lo = 0, hi = SITEMS;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (pre[mid] <= h) lo = mid; else hi = mid;
@@ -149,22 +176,34 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
 
     using SegIdx = typename std::conditional<BIG, uint32_t, uint16_t>::type;
     __shared__ LSeed seeds_lds[LSEEDS ? SEED_CAP : 1];
-    __shared__ SegIdx seg_lds[LSEEDS ? SEED_CAP + 1 : 1];
-    __shared__ __attribute__((aligned(16))) uint8_t segT_lds[LSEEDS ? SEED_CAP : 4];
     const uint32_t cap = BIG ? P.big_cap : (REV ? 0u : (uint32_t)SEED_CAP);
     LSeed *const seeds = BIG ? P.big_seeds + (size_t)blockIdx.x * cap : seeds_lds;
-    SegIdx *const seg_begin = BIG ? reinterpret_cast<SegIdx *>(P.big_seg + (size_t)blockIdx.x * (cap + 1)) : seg_lds;
-    uint8_t *const seg_T = BIG ? P.big_segT + (size_t)blockIdx.x * cap : segT_lds;
-    __shared__ uint32_t it_lo[SBLOCK], it_cnt[SBLOCK], it_pre[SBLOCK + 1], it_info[SBLOCK];
-    __shared__ uint32_t it_key[SBLOCK];
-    __shared__ uint32_t it_d[SBLOCK];   // D(p): distance to the previous usable query word (spec 2)
-    __shared__ uint32_t hq_pos[SBLOCK / 64][64 * HB];   // per-wave queue of hits for the full test
+    __shared__ uint32_t it_lo[SITEMS], it_pre[SITEMS + 1], it_info[SITEMS];
+    __shared__ uint32_t it_key[SITEMS];
+    __shared__ uint32_t it_d[SITEMS];   // D(p): distance to the previous usable query word (spec 2)
+    __shared__ __attribute__((aligned(16))) uint32_t hq_pos[SBLOCK / 64][64 * HB];   // per-wave queue of hits for the full test
     __shared__ uint8_t hq_k[SBLOCK / 64][64 * HB];
-    __shared__ uint64_t it_qlw[SBLOCK], it_qlm[AMB ? SBLOCK : 1];
     __shared__ uint64_t iso_start[ISO_LDS];
     __shared__ uint32_t iso_len[ISO_LDS], iso_gtx[ISO_LDS], iso_pre[ISO_LDS + 1];
-    __shared__ uint16_t it_iso[SBLOCK];   // isoform of each word item (it_info: p | strand << 24)
-    __shared__ uint32_t tcnt[REV ? 1 : PASS_SAMPLES], tpre[REV ? 1 : PASS_SAMPLES + 1];   // by subject sample - T0
+    __shared__ uint16_t it_iso[SITEMS];   // isoform of each word item (it_info: p | strand << 24)
+    // What only the candidate phase of a pass needs lives in arrays that are
+    // dead once the pass's hits are tested (workgroups per CU are what moves
+    // this kernel, and LDS is one of their two limits): the segment tables in
+    // the hit queue, the per-sample counts and their prefix (by subject
+    // sample - T0; the prefix's entries [0, T1 - T0) only) in it_key and
+    // it_d, the first candidates' subject transcripts in it_lo, it_pre and
+    // it_info. Too small for that (a build knob moved), they get their own.
+    constexpr bool SEG_ALIAS = LSEEDS && sizeof(hq_pos) >= (SEED_CAP + 2) * sizeof(SegIdx) + SEED_CAP;
+    constexpr bool TCNT_ALIAS = !REV && SITEMS >= PASS_SAMPLES;
+    __shared__ SegIdx seg_own[LSEEDS && !SEG_ALIAS ? SEED_CAP + 1 : 1];
+    __shared__ __attribute__((aligned(16))) uint8_t segT_own[LSEEDS && !SEG_ALIAS ? SEED_CAP : 4];
+    __shared__ uint32_t tcnt_own[REV || TCNT_ALIAS ? 1 : PASS_SAMPLES], tpre_own[REV || TCNT_ALIAS ? 1 : PASS_SAMPLES];
+    SegIdx *const seg_lds = SEG_ALIAS ? reinterpret_cast<SegIdx *>(&hq_pos[0][0]) + SEED_CAP / sizeof(SegIdx) : seg_own;
+    uint8_t *const segT_lds = SEG_ALIAS ? reinterpret_cast<uint8_t *>(&hq_pos[0][0]) : segT_own;
+    uint32_t *const tcnt = TCNT_ALIAS ? it_key : tcnt_own;
+    uint32_t *const tpre = TCNT_ALIAS ? it_d : tpre_own;
+    SegIdx *const seg_begin = BIG ? reinterpret_cast<SegIdx *>(P.big_seg + (size_t)blockIdx.x * (cap + 1)) : seg_lds;
+    uint8_t *const seg_T = BIG ? P.big_segT + (size_t)blockIdx.x * cap : segT_lds;
     __shared__ uint32_t wsum[SBLOCK / 64];
     __shared__ uint32_t sh_nseed, sh_flags, sh_rs0, sh_rs1;
     __shared__ unsigned long long sh_sbase, sh_cbase, sh_lbase;
@@ -287,108 +326,135 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
         // (inside both transcripts) extends left past p - s: not canonical
         const bool fast = stride <= 32;
         const bool lpre = !AMB && stride >= 1 && stride < W16;
-        for (uint32_t ib = 0; ib < n_items; ib += SBLOCK) {
-            const uint32_t it = ib + tid;
-            uint32_t lo = 0, cnt = 0, info = 0, key = 0;
-            uint64_t qlw = 0, qlm = 0;
-            bool ok = false;
-            int p = 0, strand = 0;
-            uint32_t ii = 0;
-            // the word's k-mer, the 32 query bases before it (canonical
-            // pre-test) and its bucket are loaded together with its DUST
-            // usability, in flight across the D(p) barriers below
-            if (it < n_items) {
-                if (!isog) {
-                    while (ii + 1 < niso && iso_pre[ii + 1] <= it) ii++;
-                } else {
-                    uint32_t lo2 = 0, hi2 = niso;   // last isoform with pre <= it
-                    while (hi2 - lo2 > 1) {
-                        const uint32_t mid = (lo2 + hi2) >> 1;
-                        if (gpre[mid] <= it) lo2 = mid; else hi2 = mid;
+        for (uint32_t ib = 0; ib < n_items; ib += SITEMS) {
+            // IPT word items per thread: item slot e * SBLOCK + tid of the round
+            uint32_t lo[IPT], cnt[IPT], info[IPT], key[IPT], ii[IPT], D[IPT];
+            bool ok[IPT];
+            int p[IPT], strand[IPT];
+            // the word's k-mer and its bucket are loaded together with its DUST
+            // usability, in flight across the D(p) barriers below (every item
+            // of the thread at once)
+#pragma unroll
+            for (int e = 0; e < IPT; e++) {
+                const uint32_t it = ib + (uint32_t)(e * SBLOCK + tid);
+                lo[e] = cnt[e] = info[e] = key[e] = ii[e] = 0;
+                ok[e] = false;
+                p[e] = strand[e] = 0;
+                if (it < n_items) {
+                    uint32_t i2 = 0;
+                    if (!isog) {
+                        while (i2 + 1 < niso && iso_pre[i2 + 1] <= it) i2++;
+                    } else {
+                        uint32_t lo2 = 0, hi2 = niso;   // last isoform with pre <= it
+                        while (hi2 - lo2 > 1) {
+                            const uint32_t mid = (lo2 + hi2) >> 1;
+                            if (gpre[mid] <= it) lo2 = mid; else hi2 = mid;
+                        }
+                        i2 = lo2;
                     }
-                    ii = lo2;
-                }
-                const uint32_t pre0 = I_pre(ii);
-                const uint32_t rem = it - pre0;
-                const uint32_t ns = (I_pre(ii + 1) - pre0) >> 1;
-                strand = rem >= ns ? 1 : 0;
-                p = (int)(rem - (strand ? ns : 0)) * stride;
-                info = (uint32_t)p | ((uint32_t)strand << 24);
-                const QGeo qg = {I_start(ii), I_len(ii)};
-                const uint64_t qp = qfwd_pos(qg, strand, total, p);
-                const uint64_t *QA = strand ? db.RC : db.F;
-                key = (uint32_t)win(QA, qp);
-                if (fast && p >= stride) {
-                    qlw = win_s(QA, (int64_t)qp - 32);
-                    if (AMB) qlm = win_s(strand ? db.ARC : db.AF, (int64_t)qp - 32);
-                }
-                ok = word_usable<AMB>(db, qg.qs, qg.Lq, strand, p, total);
-                if (ok) {
-                    const uint32_t b = key >> (32 - ix.bits);
-                    lo = ix.bucket[b];
-                    cnt = ix.bucket[b + 1];
+                    ii[e] = i2;
+                    const uint32_t pre0 = I_pre(i2);
+                    const uint32_t rem = it - pre0;
+                    const uint32_t ns = (I_pre(i2 + 1) - pre0) >> 1;
+                    strand[e] = rem >= ns ? 1 : 0;
+                    p[e] = (int)(rem - (strand[e] ? ns : 0)) * stride;
+                    info[e] = (uint32_t)p[e] | ((uint32_t)strand[e] << 24);
+                    const QGeo qg = {I_start(i2), I_len(i2)};
+                    const uint64_t qp = qfwd_pos(qg, strand[e], total, p[e]);
+                    const uint64_t *QA = strand[e] ? db.RC : db.F;
+                    key[e] = (uint32_t)win(QA, qp);
+                    ok[e] = word_usable<AMB>(db, qg.qs, qg.Lq, strand[e], p[e], total);
+                    if (ok[e]) {
+                        const uint32_t b = key[e] >> (32 - ix.bits);
+                        lo[e] = ix.bucket[b];
+                        cnt[e] = ix.bucket[b + 1];
+                    }
                 }
             }
             // D(p): the previous usable word of the same isoform and strand is
-            // item it - k (p - k s), in this batch's LDS or looked up again
-            it_d[tid] = ok ? 1u : 0u;
+            // item it - k (p - k s), in this round's LDS or (before the round's
+            // first item) looked up again
+#pragma unroll
+            for (int e = 0; e < IPT; e++) it_d[e * SBLOCK + tid] = ok[e] ? 1u : 0u;
             __syncthreads();
-            uint32_t D = (uint32_t)p + 1u;   // none: every hit is canonical
-            if (ok) {
-                for (int k = 1; p - k * stride >= 0; k++) {
-                    const bool u = tid - k >= 0 ? it_d[tid - k] != 0
-                                                : word_usable<AMB>(db, I_start(ii), I_len(ii), strand,
-                                                                   p - k * stride, total);
-                    if (u) {
-                        D = (uint32_t)(k * stride);
-                        break;
+#pragma unroll
+            for (int e = 0; e < IPT; e++) {
+                const int slot = e * SBLOCK + tid;
+                D[e] = (uint32_t)p[e] + 1u;   // none: every hit is canonical
+                if (ok[e]) {
+                    for (int k = 1; p[e] - k * stride >= 0; k++) {
+                        const bool u = slot - k >= 0 ? it_d[slot - k] != 0
+                                                     : word_usable<AMB>(db, I_start(ii[e]), I_len(ii[e]), strand[e],
+                                                                        p[e] - k * stride, total);
+                        if (u) {
+                            D[e] = (uint32_t)(k * stride);
+                            break;
+                        }
                     }
                 }
             }
             __syncthreads();
             SEED_TICK(9);
-            it_d[tid] = D;
-            if (it < n_items) {
-                if (ok) {
-                    // the bucket of the key's top bits
-                    cnt -= lo;
-                    // entries are ascending (k-mer, position) and the subject
-                    // samples a contiguous position range: two lower bounds in
-                    // the bucket (searched together) leave exactly the key's
-                    // entries in [pb0, pb1)
-                    const uint64_t K0 = ((uint64_t)key << 32) | pb0, K1 = ((uint64_t)key << 32) | pb1;
-                    uint32_t b0 = lo, n0 = cnt, b1 = lo, n1 = cnt;
-                    while (n0 | n1) {
-                        const uint32_t h0 = n0 >> 1, h1 = n1 >> 1;
-                        const uint64_t e0 = n0 ? ix.ent[b0 + h0] : 0ull, e1 = n1 ? ix.ent[b1 + h1] : 0ull;
-                        if (n0) {
-                            if (e0 < K0) { b0 += h0 + 1; n0 -= h0 + 1; } else n0 = h0;
-                        }
-                        if (n1) {
-                            if (e1 < K1) { b1 += h1 + 1; n1 -= h1 + 1; } else n1 = h1;
-                        }
+            // the bucket of the key's top bits: entries are ascending (k-mer,
+            // position) and the subject samples a contiguous position range:
+            // two lower bounds in the bucket leave exactly the key's entries
+            // in [pb0, pb1). Both searches of every item of the thread step
+            // together, their loads in flight at once.
+            uint32_t b0[IPT], n0[IPT], b1[IPT], n1[IPT];
+#pragma unroll
+            for (int e = 0; e < IPT; e++) {
+                cnt[e] -= lo[e];
+                b0[e] = b1[e] = lo[e];
+                n0[e] = n1[e] = ok[e] ? cnt[e] : 0u;
+            }
+            for (;;) {
+                uint32_t left = 0;
+#pragma unroll
+                for (int e = 0; e < IPT; e++) left |= n0[e] | n1[e];
+                if (!left) break;
+                uint64_t e0[IPT], e1[IPT];
+#pragma unroll
+                for (int e = 0; e < IPT; e++) {
+                    e0[e] = n0[e] ? ix.ent[b0[e] + (n0[e] >> 1)] : 0ull;
+                    e1[e] = n1[e] ? ix.ent[b1[e] + (n1[e] >> 1)] : 0ull;
+                }
+#pragma unroll
+                for (int e = 0; e < IPT; e++) {
+                    const uint64_t K0 = ((uint64_t)key[e] << 32) | pb0, K1 = ((uint64_t)key[e] << 32) | pb1;
+                    const uint32_t h0 = n0[e] >> 1, h1 = n1[e] >> 1;
+                    if (n0[e]) {
+                        if (e0[e] < K0) { b0[e] += h0 + 1; n0[e] -= h0 + 1; } else n0[e] = h0;
                     }
-                    lo = b0;
-                    cnt = b1 - b0;
-                } else {
-                    key = 0;
-                    qlw = qlm = 0;
+                    if (n1[e]) {
+                        if (e1[e] < K1) { b1[e] += h1 + 1; n1[e] -= h1 + 1; } else n1[e] = h1;
+                    }
                 }
             }
-            it_lo[tid] = lo;
-            it_cnt[tid] = cnt;
-            it_info[tid] = info;
-            it_iso[tid] = (uint16_t)ii;
-            it_key[tid] = key;
-            it_qlw[tid] = qlw;
-            if (AMB) it_qlm[tid] = qlm;
-            uint32_t tot;
             SEED_TICK(0);
-            it_pre[tid] = block_exscan(cnt, wsum, tot);
-            if (tid == 0) it_pre[SBLOCK] = tot;
+            uint32_t nh_round = 0;
+#pragma unroll
+            for (int e = 0; e < IPT; e++) {
+                const int slot = e * SBLOCK + tid;
+                if (ok[e]) {
+                    lo[e] = b0[e];
+                    cnt[e] = b1[e] - b0[e];
+                } else {
+                    lo[e] = cnt[e] = key[e] = 0;
+                    }
+                it_d[slot] = D[e];
+                it_lo[slot] = lo[e];
+                it_info[slot] = info[e];
+                it_iso[slot] = (uint16_t)ii[e];
+                it_key[slot] = key[e];
+                // the hits' prefix in item order: slots [e SBLOCK, (e + 1) SBLOCK) after the earlier ones
+                uint32_t tot;
+                it_pre[slot] = nh_round + block_exscan(cnt[e], wsum, tot);
+                nh_round += tot;
+            }
+            if (tid == 0) it_pre[SITEMS] = nh_round;
             __syncthreads();
             SEED_TICK(1);
-            const uint32_t nh = it_pre[SBLOCK];
+            const uint32_t nh = it_pre[SITEMS];
             const int lane = tid & 63, wid = tid >> 6;
             uint32_t *wqp = hq_pos[wid];
             uint8_t *wqk = hq_k[wid];
@@ -458,8 +524,14 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
                     if (decided) {
                     } else if (live[j] && fast && it_d[hk[j]] == (uint32_t)stride &&
                                (int)(it_info[hk[j]] & 0xFFFFFFu) >= stride) {
-                        hsw[j] = win_s(db.F, (int64_t)pos - 32) ^ it_qlw[hk[j]];
-                        if (AMB) hsm[j] = win_s(db.AF, (int64_t)pos - 32) | it_qlm[hk[j]];
+                        // (the 32 query bases before the word are read here, by
+                        // the few hits that need them, not kept per item in LDS)
+                        const uint32_t inf = it_info[hk[j]], qi = it_iso[hk[j]];
+                        const int qst = (int)(inf >> 24);
+                        const QGeo qg = {I_start(qi), I_len(qi)};
+                        const int64_t qp = (int64_t)qfwd_pos(qg, qst, total, (int)(inf & 0xFFFFFFu));
+                        hsw[j] = win_s(db.F, (int64_t)pos - 32) ^ win_s(qst ? db.RC : db.F, qp - 32);
+                        if (AMB) hsm[j] = win_s(db.AF, (int64_t)pos - 32) | win_s(qst ? db.ARC : db.AF, qp - 32);
                         hbw[j] = win_bits(db.txstart, (int64_t)pos - 63);
                     } else {
                         hsw[j] = ~0ull;
@@ -767,7 +839,7 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
             const TxInfo st = db.tx[gtx];
             if (sg == (uint32_t)tid) {
                 it_lo[tid] = (uint32_t)st.start;
-                it_cnt[tid] = st.len;
+                it_pre[tid] = st.len;
                 it_info[tid] = (uint32_t)st.sample;
             }
             const int T = st.sample - T0;
@@ -775,11 +847,13 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
             atomicAdd(&tcnt[T], 1u);
         }
         __syncthreads();
-        {
+        for (int c0 = 0, before = 0; c0 < NT; c0 += SBLOCK) {   // (uniform: NT is the block's)
             uint32_t tot;
-            const uint32_t v = tid < NT ? tcnt[tid] : 0u;
-            const uint32_t pre = block_exscan(v, wsum, tot);
-            if (tid < NT) tpre[tid] = pre;
+            const int T = c0 + tid;
+            const uint32_t v = T < NT ? tcnt[T] : 0u;
+            const uint32_t pre = (uint32_t)before + block_exscan(v, wsum, tot);
+            if (T < NT) tpre[T] = pre;
+            before += (int)tot;
         }
         if (tid == 0) {
             sh_sbase = sb_claim;
@@ -867,7 +941,7 @@ __global__ __launch_bounds__(SBLOCK, REV ? RC_SEED_REV_WAVES : RC_SEED_WAVES) vo
                     TxInfo st;
                     if (c0 == 0) {
                         st.start = it_lo[tid];
-                        st.len = it_cnt[tid];
+                        st.len = it_pre[tid];
                         st.sample = (int)it_info[tid];
                     } else {
                         st = db.tx[gtx];
