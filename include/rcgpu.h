@@ -50,7 +50,8 @@ extern "C" {
  *   samples in a neighbour-joining tree 1024 (rc_nj, rc_resample_trees)
  *   splits in a census            2^31 - 1 (rc_split_census, rc_tree_rf)
  *   trees in a pairwise distance matrix 8192 (rc_tree_rf)
- *   samples in a principal coordinates analysis 128 (rc_pcoa, rc_resample_pcoa) */
+ *   samples in a principal coordinates analysis 128 (rc_pcoa, rc_resample_pcoa)
+ *   samples in a group test       128 (rc_group_test, rc_resample_group_test) */
 #define RC_E_IO (-8)         /* file could not be written */
 
 typedef struct rc_engine rc_engine;
@@ -170,6 +171,8 @@ typedef struct rc_timing {
     double split_ms;          /* device time of the kernels that the last rc_split_census / rc_tree_rf ran: the
                                  census when that call built it, the gather of the distinct splits, the
                                  distances (the copies back are outside it) */
+    double group_ms;          /* device time of the last rc_group_test / rc_resample_group_test's ranking and
+                                 test kernels (uploads and the copies back are outside it) */
 } rc_timing;
 
 void rc_default_opts(rc_opts *opts);
@@ -468,6 +471,51 @@ int rc_pcoa(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, int32_t k
 int rc_resample_pcoa(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
                      int32_t n, int32_t k, int32_t max_sweeps, double *values, double *vectors, int32_t *sweeps,
                      uint8_t *valid);
+
+/* ---- group tests: PERMANOVA and ANOSIM with label permutations --------------
+ * Do the sample groups separate? Of matrix D[n][n] only i < j is read.
+ * labels[n] puts every sample into one of n_groups groups 0..n_groups-1, none
+ * empty; perm_labels holds n_perm rearrangements of labels, n each (the same
+ * rows serve every replicate). Float64 with a fixed operation order (DESIGN.md
+ * section 2), so that two label vectors that describe the same partition give
+ * the same bits. With v = D[i][j]^2 (PERMANOVA) or v = twice the average rank
+ * of D[i][j] among the M = n (n - 1) / 2 distances, an integer (ANOSIM):
+ *   t[i] = sum over j ascending of v[j][i] where labels[j] == labels[i], j != i
+ *   S    = the sum of x[i] = t[i] / (2 n_g(i)) (PERMANOVA; n_g(i) the size of
+ *          i's group) or x[i] = t[i] (ANOSIM), x padded with zeros to a power
+ *          of two and halved (x[0:h] + x[h:2h]) until one value is left
+ * RC_GROUP_PERMANOVA (Anderson 2001): SS_W = S, SS_T = S with everything in one
+ * group, F = ((SS_T - SS_W) / (a - 1)) / (SS_W / (n - a)) with a = n_groups.
+ * RC_GROUP_ANOSIM (Clarke 1993): W2 = S / 2, the twice-ranks of the m_W
+ * within-group pairs; r_W = W2 / (2 m_W), r_B = (M (M + 1) - W2) / (2 (M -
+ * m_W)), R = (r_B - r_W) / (M / 2).
+ *   stat[r]      F or R of the observed labels
+ *   n_ge[r]      permutations whose statistic is >= the observed one (F as
+ *                computed, a comparison with NaN counts nothing; W2 <= the
+ *                observed W2 on the integers): p = (1 + n_ge) / (1 + n_perm)
+ *   total[r]     SS_T, or M (M + 1); within[r]: SS_W, or W2
+ *   perm_stat    the statistic of every permutation, n_rep x n_perm
+ *   valid[r]     0 for a matrix with a non-finite entry above its diagonal: its
+ *                stat, total, within and perm_stat are NaN, its n_ge 0
+ * Any output may be NULL. RC_E_LIMIT: n > 128 (checked first; the matrix lives
+ * in LDS), or n_rep x ceil(n_perm / 120) >= 2^31. RC_E_ARG: NULL D or labels,
+ * NULL perm_labels with n_perm > 0, n_rep < 1, n_perm < 0, an unknown method,
+ * n_groups < 2 or >= n, a label outside 0..n_groups-1, an empty group, a row of
+ * perm_labels that is not a rearrangement of labels. RC_E_NO_IDEAL after
+ * filling the outputs when some matrix is invalid.
+ * rc_group_test: n_rep caller matrices (host, n_rep x n x n), on an engine in
+ * any state. rc_resample_group_test: rc_resample's replicate matrices for
+ * order[n], which never leave the device; an order that names some of the
+ * samples tests that sub-matrix (a pairwise test of two groups). */
+#define RC_GROUP_PERMANOVA 0
+#define RC_GROUP_ANOSIM 1
+int rc_group_test(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, const int32_t *labels, int32_t n_groups,
+                  const int32_t *perm_labels, int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge,
+                  double *total, double *within, double *perm_stat, uint8_t *valid);
+int rc_resample_group_test(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp,
+                           const int32_t *order, int32_t n, const int32_t *labels, int32_t n_groups,
+                           const int32_t *perm_labels, int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge,
+                           double *total, double *within, double *perm_stat, uint8_t *valid);
 int rc_timings(rc_engine *eng, rc_timing *t);
 /* The DUST mask of sample `s` after rc_run / rc_align: one byte per base of
  * its concatenated transcripts (1 = masked query base, spec 1b of the oracle);

@@ -1,6 +1,7 @@
 // Analyses of a finished engine's graph: per-component tables, bootstrap
-// resampling, neighbour-joining trees, the census of their splits and
-// principal coordinates (kernels: components.hip, nj.hip, splits.hip, pcoa.hip).
+// resampling, neighbour-joining trees, the census of their splits, principal
+// coordinates and group tests (kernels: components.hip, nj.hip, splits.hip,
+// pcoa.hip, groups.hip).
 #include "engine.h"
 
 // ------------------------------------------------------------------------
@@ -666,6 +667,147 @@ int rc_resample_pcoa(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint6
     e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
     if (stat[0]) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     if (stat[1]) return pcoa_unconverged();
+    return RC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// group tests (groups.hip)
+// ------------------------------------------------------------------------
+
+static const int GROUP_MAX_SAMPLES = 128;
+
+// The argument checks of rc_group_test / rc_resample_group_test (no device
+// work). lab8: the observed labels, then the n_perm permuted rows, one byte
+// each; *m_within: the within-group pairs.
+static int group_check(int32_t n_rep, int32_t n, const int32_t *labels, int32_t a, const int32_t *perm, int32_t n_perm,
+                       int32_t method, std::vector<uint8_t> &lab8, uint32_t *m_within)
+{
+    if (n > GROUP_MAX_SAMPLES) return fail(RC_E_LIMIT, "more than 128 samples in a group test");
+    if (!labels || (n_perm > 0 && !perm)) return fail(RC_E_ARG, "null argument");
+    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
+    if (n_perm < 0) return fail(RC_E_ARG, "n_perm must be >= 0");
+    if (method != RC_GROUP_PERMANOVA && method != RC_GROUP_ANOSIM) return fail(RC_E_ARG, "unknown group test");
+    if (a < 2 || a >= n) return fail(RC_E_ARG, "a group test needs 2 <= n_groups < n");
+    if (((uint64_t)n_perm + GROUP_PERM_CHUNK - 1) / GROUP_PERM_CHUNK * (uint64_t)n_rep >> 31)
+        return fail(RC_E_LIMIT, "n_rep x permutations beyond the group test's grid");
+    std::vector<int32_t> size(a, 0), seen(a);
+    lab8.resize(((size_t)n_perm + 1) * n);
+    for (int i = 0; i < n; i++) {
+        if (labels[i] < 0 || labels[i] >= a) return fail(RC_E_ARG, "a label outside 0..n_groups-1");
+        size[labels[i]]++;
+        lab8[i] = (uint8_t)labels[i];
+    }
+    uint32_t mw = 0;
+    for (int g = 0; g < a; g++) {
+        if (!size[g]) return fail(RC_E_ARG, "an empty group");
+        mw += (uint32_t)size[g] * (uint32_t)(size[g] - 1) / 2;
+    }
+    for (int64_t p = 0; p < n_perm; p++) {
+        const int32_t *row = perm + p * n;
+        uint8_t *out = lab8.data() + (size_t)(p + 1) * n;
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int i = 0; i < n; i++) {
+            if (row[i] < 0 || row[i] >= a || ++seen[row[i]] > size[row[i]])
+                return fail(RC_E_ARG, "a row of perm_labels is not a rearrangement of labels");
+            out[i] = (uint8_t)row[i];
+        }
+    }
+    *m_within = mw;
+    return RC_OK;
+}
+
+// The test of the n_rep matrices at dD (device, n x n each); the arguments have
+// passed group_check. Events EV_GROUP0, EV_GROUP1. *invalid: the number of
+// matrices with a non-finite entry.
+static int group_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t a, uint32_t m_within,
+                        const std::vector<uint8_t> &lab8, int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge,
+                        double *total, double *within, double *perm_stat, uint8_t *valid, uint32_t *invalid)
+{
+    rc_engine::Analysis &an = e->an;
+    const size_t R = (size_t)n_rep, np = perm_stat ? R * (size_t)n_perm : 0;
+    const bool anosim = method == RC_GROUP_ANOSIM;
+    int lds_max = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
+    if (std::max(group_lds_bytes(method, n), anosim ? group_rank_lds_bytes(n) : 0) + 4096 > (size_t)lds_max)
+        return fail(RC_E_LIMIT, "this device's LDS does not hold a matrix of " + std::to_string(n) + " samples");
+    CHK(an.d_gt_labels.ensure(lab8.size()));
+    CHK(an.d_gt_stat.ensure(R));
+    CHK(an.d_gt_total.ensure(R));
+    CHK(an.d_gt_within.ensure(R));
+    CHK(an.d_gt_nge.ensure(R));
+    CHK(an.d_gt_valid.ensure(R));
+    if (np) CHK(an.d_gt_perm.ensure(np));
+    if (anosim) CHK(an.d_gt_rank.ensure(R * (size_t)n * n));
+    HIPCHK(hipMemcpyAsync(an.d_gt_labels.p, lab8.data(), lab8.size(), hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemsetAsync(an.d_gt_nge.p, 0, R * 4, e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_GROUP0], e->st));
+    if (anosim) {
+        const hipError_t err = launch_group_rank(dD, n_rep, n, an.d_gt_rank.p, an.d_gt_valid.p, e->st);
+        if (err != hipSuccess)
+            return fail(RC_E_HIP, std::string("group_rank_kernel (") + std::to_string(group_rank_lds_bytes(n)) +
+                                      " bytes of LDS): " + hipGetErrorString(err));
+    }
+    const hipError_t err =
+        launch_group_test(method, anosim ? (const void *)an.d_gt_rank.p : (const void *)dD, an.d_gt_valid.p, n_rep, n, a,
+                          m_within, an.d_gt_labels.p, an.d_gt_labels.p + n, n_perm, an.d_gt_stat.p, an.d_gt_nge.p,
+                          an.d_gt_total.p, an.d_gt_within.p, np ? an.d_gt_perm.p : nullptr, an.d_gt_valid.p, e->st);
+    if (err != hipSuccess)
+        return fail(RC_E_HIP, std::string("group_kernel (") + std::to_string(group_lds_bytes(method, n)) +
+                                  " bytes of LDS): " + hipGetErrorString(err));
+    HIPCHK(hipEventRecord(e->ev[EV_GROUP1], e->st));
+    std::vector<uint8_t> hv(R);
+    if (stat) HIPCHK(hipMemcpyAsync(stat, an.d_gt_stat.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (n_ge) HIPCHK(hipMemcpyAsync(n_ge, an.d_gt_nge.p, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (total) HIPCHK(hipMemcpyAsync(total, an.d_gt_total.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (within) HIPCHK(hipMemcpyAsync(within, an.d_gt_within.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (np) HIPCHK(hipMemcpyAsync(perm_stat, an.d_gt_perm.p, np * 8, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(hv.data(), an.d_gt_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.group_ms = ev_ms(e, EV_GROUP0, EV_GROUP1);
+    uint32_t bad = 0;
+    for (size_t r = 0; r < R; r++) bad += !hv[r];
+    if (valid) std::copy(hv.begin(), hv.end(), valid);
+    *invalid = bad;
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_group_test(rc_engine *e, const double *D, int32_t n_rep, int32_t n, const int32_t *labels, int32_t n_groups,
+                  const int32_t *perm_labels, int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge,
+                  double *total, double *within, double *perm_stat, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    std::vector<uint8_t> lab8;
+    uint32_t mw = 0, invalid = 0;
+    CHK(group_check(n_rep, n, labels, n_groups, perm_labels, n_perm, method, lab8, &mw));
+    if (!D) return fail(RC_E_ARG, "null argument");
+    CHK(set_device(e));
+    const size_t nd = (size_t)n_rep * n * n;
+    CHK(e->an.d_gt_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->an.d_gt_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
+    CHK(group_device(e, e->an.d_gt_in.p, n_rep, n, n_groups, mw, lab8, n_perm, method, stat, n_ge, total, within,
+                     perm_stat, valid, &invalid));
+    if (invalid) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no group test for it");
+    return RC_OK;
+}
+
+int rc_resample_group_test(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                           int32_t n, const int32_t *labels, int32_t n_groups, const int32_t *perm_labels,
+                           int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge, double *total, double *within,
+                           double *perm_stat, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    std::vector<uint8_t> lab8;
+    uint32_t mw = 0, invalid = 0;
+    CHK(group_check(n_rep, n, labels, n_groups, perm_labels, n_perm, method, lab8, &mw));
+    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
+    CHK(group_device(e, e->d_dist.p, n_rep, n, n_groups, mw, lab8, n_perm, method, stat, n_ge, total, within, perm_stat,
+                     valid, &invalid));
+    e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
+    if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;
 }
 

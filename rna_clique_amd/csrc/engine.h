@@ -189,6 +189,7 @@ enum Ev {
     EV_NJ0 = 14, EV_NJ1 = 15,               // nj_device: the trees and the split support (nj_ms)
     EV_PCOA0 = 16, EV_PCOA1 = 17,           // pcoa_device: the ordinations (pcoa_ms)
     EV_SPLIT0 = 18, EV_SPLIT1 = 19,         // rc_split_census, rc_tree_rf: the census and RF kernels (split_ms)
+    EV_GROUP0 = 20, EV_GROUP1 = 21,         // group_device: the ranking and test kernels (group_ms)
     EV_N
 };
 // rc_engine::evd: DUST on the second stream
@@ -412,6 +413,11 @@ struct rc_engine {
         DBuf<int32_t> d_pcoa_sweeps;
         DBuf<uint8_t> d_pcoa_valid;
         DBuf<unsigned int> d_pcoa_stat;
+        // group tests (groups.hip): input matrices of rc_group_test, the observed
+        // and permuted labels (one byte each), ANOSIM's twice-ranks and the results
+        DBuf<double> d_gt_in, d_gt_stat, d_gt_total, d_gt_within, d_gt_perm;
+        DBuf<uint8_t> d_gt_labels, d_gt_valid;
+        DBuf<uint32_t> d_gt_rank, d_gt_nge;
     };
     Analysis an;
 

@@ -1,5 +1,5 @@
 // The host entry points of the kernel files: every non-static host function
-// that kernels.hip, components.hip, nj.hip, splits.hip, pcoa.hip, sort.hip,
+// that kernels.hip, components.hip, nj.hip, splits.hip, pcoa.hip, groups.hip, sort.hip,
 // seed.hip, align.hip, rows.hip, finish.hip, extend.hip, group.hip and dust.hip define,
 // one section per unit, declared here and nowhere else. The defining files
 // include this header too, so a definition whose return type drifts from its
@@ -78,6 +78,15 @@ int pcoa_ld(int);
 size_t pcoa_lds_bytes(int);
 hipError_t launch_pcoa(const double *, int, int, int, int, double *, double *, int32_t *, uint8_t *, unsigned int *,
                        hipStream_t);
+// groups.hip
+enum { GROUP_PERMANOVA = 0, GROUP_ANOSIM = 1 };   // rcgpu.h: RC_GROUP_PERMANOVA, RC_GROUP_ANOSIM
+enum { GROUP_PERM_CHUNK = 120 };                  // permutations per workgroup
+size_t group_lds_bytes(int, int);
+size_t group_rank_lds_bytes(int);
+hipError_t launch_group_rank(const double *, int, int, uint32_t *, uint8_t *, hipStream_t);
+hipError_t launch_group_test(int, const void *, const uint8_t *, int, int, int, uint32_t, const uint8_t *,
+                             const uint8_t *, int, double *, uint32_t *, double *, double *, double *, uint8_t *,
+                             hipStream_t);
 // sort.hip
 uint64_t os_status_words(uint64_t n);
 uint64_t os_scratch_words(uint64_t n);

@@ -537,6 +537,78 @@ class Engine:
             nat.check(code)
         return [self.labels[i] for i in order], PCoAEigen(**bufs)
 
+    # --------------------------------------------------------- group tests
+    @staticmethod
+    def _group_args(r, m, labels, perm_labels, method, perm_stats):
+        """The label arrays as the library reads them (it checks them), the
+        output buffers and the tail of rc_group_test's arguments."""
+        from .groups import method_code
+        code = method_code(method)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim != 1 or len(lab) != m:
+            raise ValueError("one label per sample")
+        perms = np.zeros((0, m), dtype=np.int32) if perm_labels is None else \
+            np.ascontiguousarray(perm_labels, dtype=np.int32)
+        if perms.size == 0:
+            perms = perms.reshape(0, m)
+        if perms.ndim != 2 or perms.shape[1] != m:
+            raise ValueError("perm_labels must have shape (permutations, N)")
+        p = len(perms)
+        bufs = {"stat": np.zeros(r, dtype=np.float64), "n_ge": np.zeros(r, dtype=np.uint32),
+                "total": np.zeros(r, dtype=np.float64), "within": np.zeros(r, dtype=np.float64),
+                "perm_stat": np.zeros((r, p), dtype=np.float64) if perm_stats else None,
+                "valid": np.zeros(r, dtype=np.uint8)}
+        vp = ctypes.c_void_p
+        ptr = lambda a: None if a is None else a.ctypes.data_as(vp)   # noqa: E731
+        n_groups = int(lab.max()) + 1 if len(lab) else 0
+        tail = (ptr(lab), n_groups, ptr(perms) if p else None, p, code, *(ptr(a) for a in bufs.values()))
+        return (lab, perms), n_groups, bufs, tail
+
+    @staticmethod
+    def _group_result(method, m, n_groups, perms, bufs):
+        from .groups import GroupTestResult
+        return GroupTestResult.from_counts(method, m, n_groups, len(perms), bufs["stat"], bufs["n_ge"], bufs["total"],
+                                           bufs["within"], bufs["valid"], bufs["perm_stat"])
+
+    def group_test(self, matrices, labels, perm_labels=None, method="permanova", *, perm_stats=False,
+                   allow_nan=False):
+        """PERMANOVA ("permanova") or ANOSIM ("anosim") of distance matrices
+        (R, N, N) or (N, N), of which only the part above the diagonal is read
+        (rc_group_test; the engine may be in any state; N <= 128, else
+        groups.group_test_host). labels (N,): group numbers 0..a-1
+        (groups.encode_grouping), 2 <= a < N; perm_labels (P, N): rearrangements
+        of labels (groups.permuted_labels), the same rows for every matrix;
+        none: the statistics only. Returns groups.GroupTestResult with one
+        entry per matrix, and the permutations' statistics with perm_stats.
+        Raises NativeError(RC_E_NO_IDEAL) when a matrix has a non-finite
+        entry, unless allow_nan (that replicate is then NaN and flagged in
+        `valid`)."""
+        d = self._matrices(matrices)
+        r, m = d.shape[0], d.shape[1]
+        (lab, perms), n_groups, bufs, tail = self._group_args(r, m, labels, perm_labels, method, perm_stats)
+        code = nat.lib().rc_group_test(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, *tail)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return self._group_result(method, m, n_groups, perms, bufs)
+
+    def resample_group_test(self, weights, labels, perm_labels=None, order=None, method="permanova", *,
+                            perm_stats=False, allow_nan=False):
+        """The group test of every replicate of resample(weights, order): the
+        matrices stay on the device (rc_resample_group_test). labels[i] is the
+        group of sample order[i]; an order that names some of the samples tests
+        their sub-matrix. Returns (labels of the samples, GroupTestResult).
+        Errors as group_test(); RC_E_NO_IDEAL: a replicate has a pair without
+        rows."""
+        w, order = self._weights(weights), self._order(order)
+        m, r = len(order), w.shape[0]
+        (lab, perms), n_groups, bufs, tail = self._group_args(r, m, labels, perm_labels, method, perm_stats)
+        vp = ctypes.c_void_p
+        code = nat.lib().rc_resample_group_test(self._h, w.ctypes.data_as(vp), r, w.shape[1], order.ctypes.data_as(vp),
+                                                m, *tail)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return [self.labels[i] for i in order], self._group_result(method, m, n_groups, perms, bufs)
+
     def dust_mask(self, s):
         """DUST mask of sample s (uint8 per base, 1 = masked query base)."""
         return self._sized(nat.lib().rc_dust_mask, np.uint8, int(s))

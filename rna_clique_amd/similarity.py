@@ -562,6 +562,86 @@ class SampleSimilarity:
         w = bootstrap_weights(self.engine.n_components(), n_rep, seed)
         return ref, self.resampled_pcoa(w, dims)
 
+    # ------------------------------------------------------- group tests
+    def _group_design(self, grouping, permutations, seed, samples=None):
+        """(engine order, labels, group names, permuted labels) of `samples`
+        (default: all of them, in this object's order)."""
+        from .groups import MAX_GPU_SAMPLES, encode_grouping, permuted_labels
+        samples = self.samples if samples is None else samples
+        if len(samples) > MAX_GPU_SAMPLES:
+            raise ValueError(f"more than {MAX_GPU_SAMPLES} samples: use rna_clique_amd.groups.group_test_host on "
+                             "get_dissimilarity_matrix() or on the resampled matrices")
+        labels, names = encode_grouping(samples, grouping)
+        if not 2 <= len(names) < len(samples):
+            raise ValueError("a group test needs at least 2 groups and fewer groups than samples")
+        index = {s: i for i, s in enumerate(self.labels)}
+        order = [index[s] for s in samples]
+        return order, labels, names, permuted_labels(labels, permutations, seed)
+
+    def resampled_group_test(self, weights, grouping, method="permanova", permutations=999, seed=0, *,
+                             perm_stats=False, samples=None):
+        """The group test (groups.GroupTestResult, one entry per row of
+        `weights`) of resampled_dissimilarity_matrices(weights), run on the GPU
+        without the matrices leaving it. `grouping`: as groups.encode_grouping
+        takes it; the permuted labels are groups.permuted_labels(labels,
+        permutations, seed), the same rows for every replicate. `samples`: test
+        the sub-matrix of these samples only. Raises NoIdealComponentsError
+        when a replicate leaves a pair without rows."""
+        order, labels, _, perms = self._group_design(grouping, permutations, seed, samples)
+        try:
+            return self.engine.resample_group_test(weights, labels, perms, order, method, perm_stats=perm_stats)[1]
+        except nat.NativeError as e:
+            if e.code == nat.RC_E_NO_IDEAL:
+                raise NoIdealComponentsError() from e
+            raise
+
+    def _group_test(self, grouping, method, permutations, seed, samples=None):
+        c = self.engine.n_components()
+        if c == 0:
+            raise NoIdealComponentsError()
+        return self.resampled_group_test(np.ones((1, c), dtype=np.uint16), grouping, method, permutations, seed,
+                                         samples=samples).first()
+
+    def permanova(self, grouping, permutations=999, seed=0):
+        """PERMANOVA (Anderson 2001) of get_dissimilarity_matrix() -- the
+        replicate of all-ones weights, which is that matrix bit for bit -- for
+        the groups of `grouping`, on the GPU: what skbio.stats.distance.
+        permanova answers. Returns groups.GroupTestResult with scalar fields:
+        statistic (pseudo-F), p_value, r2."""
+        return self._group_test(grouping, "permanova", permutations, seed)
+
+    def anosim(self, grouping, permutations=999, seed=0):
+        """ANOSIM (Clarke 1993) of get_dissimilarity_matrix(), as permanova():
+        statistic is R, from average ranks."""
+        return self._group_test(grouping, "anosim", permutations, seed)
+
+    def bootstrap_group_test(self, grouping, n_rep, seed=0, method="permanova", permutations=999):
+        """(the test of the full matrix, the test of each of n_rep bootstrap
+        replicates over the ideal components): how stable the statistic and its
+        p-value are under resampling. Both use the same permuted labels; the
+        replicate matrices never leave the device."""
+        ref = self._group_test(grouping, method, permutations, seed)
+        w = bootstrap_weights(self.engine.n_components(), n_rep, seed)
+        return ref, self.resampled_group_test(w, grouping, method, permutations, seed)
+
+    def pairwise_group_tests(self, grouping, method="permanova", permutations=999, seed=0) -> dict:
+        """One test per pair of groups, on the sub-matrix of the two groups'
+        samples: {(group, other group): GroupTestResult}. The p-values are as
+        computed, one per test: no multiple-testing correction is applied. A
+        pair of two single samples cannot be tested and is left out."""
+        from .groups import encode_grouping
+        labels, names = encode_grouping(self.samples, grouping)
+        out = {}
+        for i in range(len(names)):
+            for j in range(i + 1, len(names)):
+                sub = [s for s, g in zip(self.samples, labels) if g in (i, j)]
+                if len(sub) < 3:
+                    continue
+                which = {s: names[g] for s, g in zip(self.samples, labels)}
+                out[(names[i], names[j])] = self._group_test({s: which[s] for s in sub}, method, permutations, seed,
+                                                             samples=sub)
+        return out
+
 
 def _table_sums(df: pd.DataFrame):
     """(sum nident, sum length - sum gaps) of one gene matches table, as exact
