@@ -51,7 +51,9 @@ extern "C" {
  *   splits in a census            2^31 - 1 (rc_split_census, rc_tree_rf)
  *   trees in a pairwise distance matrix 8192 (rc_tree_rf)
  *   samples in a principal coordinates analysis 128 (rc_pcoa, rc_resample_pcoa)
- *   samples in a group test       128 (rc_group_test, rc_resample_group_test) */
+ *   samples in a group test       128 (rc_group_test, rc_resample_group_test)
+ *   samples in a dispersion test  128 (rc_group_dispersion, rc_resample_group_dispersion)
+ *   samples in a Mantel test      128 (rc_mantel, rc_resample_mantel) */
 #define RC_E_IO (-8)         /* file could not be written */
 
 typedef struct rc_engine rc_engine;
@@ -173,6 +175,10 @@ typedef struct rc_timing {
                                  distances (the copies back are outside it) */
     double group_ms;          /* device time of the last rc_group_test / rc_resample_group_test's ranking and
                                  test kernels (uploads and the copies back are outside it) */
+    double disp_ms;           /* device time of the last rc_group_dispersion / rc_resample_group_dispersion's
+                                 kernel (uploads and the copies back are outside it) */
+    double mantel_ms;         /* device time of the last rc_mantel / rc_resample_mantel's ranking and test kernels
+                                 (uploads and the copies back are outside it) */
 } rc_timing;
 
 void rc_default_opts(rc_opts *opts);
@@ -516,6 +522,88 @@ int rc_resample_group_test(rc_engine *eng, const uint16_t *weights, int32_t n_re
                            const int32_t *order, int32_t n, const int32_t *labels, int32_t n_groups,
                            const int32_t *perm_labels, int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge,
                            double *total, double *within, double *perm_stat, uint8_t *valid);
+
+/* ---- PERMDISP: are the groups equally spread? ------------------------------
+ * The companion of PERMANOVA (Anderson 2006, centroid form; vegan's betadisper,
+ * skbio.stats.distance.permdisp with test="centroid"): PERMANOVA cannot tell a
+ * difference in location from one in spread. D, labels, perm_labels and the
+ * conventions are those of rc_group_test. With v = D[i][j]^2, n_g(i) the size
+ * of i's group and every sum over j ascending, own-group terms only:
+ *   t[i] = sum of v[j][i];  b[i] = sum of t[j]
+ *   z[i] = sqrt(|t[i] / n_g(i) - b[i] / (2 n_g(i)^2)|): the distance of sample i
+ *          to its group's centroid in the full principal-coordinate space, the
+ *          imaginary axes subtracted; it follows from the squared distances
+ *          alone, no eigensolver is involved. A singleton has z = 0.
+ *   m[i] = (sum of z[j]) / n_g(i);  SS_W = H((z - m)^2);  zbar = H(z) / n;
+ *   SS_T = H((z - zbar)^2), H the halving sum of rc_group_test's S
+ *   F    = ((SS_T - SS_W) / (a - 1)) / (SS_W / (n - a)), the one-way ANOVA F of z
+ * A permutation recomputes everything from its labels, centroids included.
+ *   stat[r]      F of the observed labels (whatever IEEE arithmetic gives when
+ *                SS_W is 0)
+ *   n_ge[r]      permutations with F >= the observed F (a comparison with NaN
+ *                counts nothing): p = (1 + n_ge) / (1 + n_perm)
+ *   total[r], within[r]   SS_T and SS_W of z
+ *   perm_stat    F of every permutation, n_rep x n_perm
+ *   dist         the observed z, n_rep x n
+ *   valid[r]     0 for a matrix with a non-finite entry above its diagonal: its
+ *                stat, total, within, perm_stat and dist are NaN, its n_ge 0
+ * Any output may be NULL. The argument checks and return codes are those of
+ * rc_group_test (there is no method; the grid limit is n_rep x ceil(n_perm /
+ * 124) >= 2^31). Not included: the spatial-median variant, vegan's permutation
+ * of residuals, confidence ellipsoids. */
+int rc_group_dispersion(rc_engine *eng, const double *D, int32_t n_rep, int32_t n, const int32_t *labels,
+                        int32_t n_groups, const int32_t *perm_labels, int32_t n_perm, double *stat, uint32_t *n_ge,
+                        double *total, double *within, double *perm_stat, double *dist, uint8_t *valid);
+int rc_resample_group_dispersion(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp,
+                                 const int32_t *order, int32_t n, const int32_t *labels, int32_t n_groups,
+                                 const int32_t *perm_labels, int32_t n_perm, double *stat, uint32_t *n_ge,
+                                 double *total, double *within, double *perm_stat, double *dist, uint8_t *valid);
+
+/* ---- the Mantel test: do two distance matrices agree? ----------------------
+ * The permutation correlation of every replicate matrix X[r] (n x n) with one
+ * matrix Y (n x n), over the M = n (n - 1) / 2 entries above the diagonal
+ * (skbio.stats.distance.mantel). Of a matrix only i < j is read. perms holds
+ * n_perm permutations of 0..n-1, n each (the same rows serve every replicate);
+ * permutation p rearranges X's rows and columns together:
+ *   r(p) = corr(X[p(i)][p(j)], Y[i][j]) over i < j; the identity gives stat.
+ * Fixed operation order. With every sum over j ascending
+ * and H the halving sum of rc_group_test's S:
+ * RC_MANTEL_PEARSON (float64): mx = H(rs) / (n (n - 1)) with rs[i] the sum of
+ *   column i of the mirrored X; xc = X - mx off the diagonal, 0 on it; sxx =
+ *   H(q), q[i] the sum of xc[j][i]^2; yc, syy likewise; C(p) = H(c), c[i] the
+ *   sum of xc[p(j)][p(i)] yc[j][i]; r = C / sqrt(sxx syy), exactly 1 for Y = X.
+ *   The counts compare r as computed.
+ * RC_MANTEL_SPEARMAN (integers): a, b the twice-ranks (rc_group_test's ANOSIM
+ *   ranks) of X[r] and Y; Sab(p) the sum over i < j of a[p(i)][p(j)] b[i][j];
+ *   num = M Sab - Sa Sb, vx = M Saa - Sa^2, vy = M Sbb - Sb^2 in 64 bits;
+ *   r = num / sqrt(vx vy) in float64. The counts compare num, so they are
+ *   exact with ties too.
+ *   stat[r]      r of the identity
+ *   n_ge[r], n_le[r], n_abs_ge[r]   permutations with r(p) >= stat, r(p) <= stat,
+ *                |r(p)| >= |stat|: p = (1 + count) / (1 + n_perm) for the
+ *                alternatives "greater", "less" and "two-sided"
+ *   perm_stat    r of every permutation, n_rep x n_perm
+ *   valid[r]     0 for an X[r] with a non-finite entry above its diagonal: its
+ *                stat and perm_stat are NaN, its counts 0
+ * An X[r] or a Y that is constant above the diagonal has no correlation: stat
+ * and perm_stat NaN, counts 0, valid 1.
+ * Any output may be NULL. RC_E_LIMIT: n > 128 (checked first; X lives in LDS),
+ * or n_rep x ceil(n_perm / 124) >= 2^31. RC_E_ARG: NULL X or Y, NULL perms with
+ * n_perm > 0, n < 3, n_rep < 1, n_perm < 0, an unknown method, a non-finite
+ * entry above Y's diagonal, a row of perms that is not a rearrangement of
+ * 0..n-1. RC_E_NO_IDEAL after filling the outputs when some X[r] is invalid.
+ * rc_mantel: n_rep caller matrices (host), on an engine in any state.
+ * rc_resample_mantel: rc_resample's replicate matrices for order[n], which
+ * never leave the device; Y is in order's sample order. Not included: the
+ * partial Mantel test. */
+#define RC_MANTEL_PEARSON 0
+#define RC_MANTEL_SPEARMAN 1
+int rc_mantel(rc_engine *eng, const double *X, int32_t n_rep, int32_t n, const double *Y, const int32_t *perms,
+              int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge, uint32_t *n_le, uint32_t *n_abs_ge,
+              double *perm_stat, uint8_t *valid);
+int rc_resample_mantel(rc_engine *eng, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                       int32_t n, const double *Y, const int32_t *perms, int32_t n_perm, int32_t method, double *stat,
+                       uint32_t *n_ge, uint32_t *n_le, uint32_t *n_abs_ge, double *perm_stat, uint8_t *valid);
 int rc_timings(rc_engine *eng, rc_timing *t);
 /* The DUST mask of sample `s` after rc_run / rc_align: one byte per base of
  * its concatenated transcripts (1 = masked query base, spec 1b of the oracle);

@@ -27,6 +27,8 @@ RC_E_LIMIT = -7
 
 RC_GROUP_PERMANOVA = 0
 RC_GROUP_ANOSIM = 1
+RC_MANTEL_PEARSON = 0
+RC_MANTEL_SPEARMAN = 1
 
 
 class RcOpts(ctypes.Structure):
@@ -92,7 +94,8 @@ class RcTiming(ctypes.Structure):
         "band_bound", "maxhsp_bound", "ext_second", "near_index", "reverse_seeds", "ext_slides", "ext_wide", "dev_bytes",
         "dev_peak_bytes", "defer_length", "defer_gaveup", "defer_outside", "index_reused",
         "ext_retries", "load_ms", "align_wall_ms", "host_wait_ms", "later_seeds", "later_whole",
-        "index_fb_ranges", "index_fb_keys", "resample_ms", "nj_ms", "pcoa_ms", "split_ms", "group_ms")]
+        "index_fb_ranges", "index_fb_keys", "resample_ms", "nj_ms", "pcoa_ms", "split_ms", "group_ms",
+        "disp_ms", "mantel_ms")]
 
 
 assert HSP_DTYPE.itemsize == ctypes.sizeof(RcHsp)
@@ -155,6 +158,14 @@ SIGNATURES = {
     "rc_resample_group_test": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, VP,
                                               ctypes.c_int32, VP, ctypes.c_int32, ctypes.c_int32, VP, VP, VP, VP, VP,
                                               VP]),
+    "rc_group_dispersion": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int32, VP, ctypes.c_int32, VP,
+                                           ctypes.c_int32, VP, VP, VP, VP, VP, VP, VP]),
+    "rc_resample_group_dispersion": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, VP,
+                                                    ctypes.c_int32, VP, ctypes.c_int32, VP, VP, VP, VP, VP, VP, VP]),
+    "rc_mantel": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int32, VP, VP, ctypes.c_int32, ctypes.c_int32, VP, VP, VP,
+                                 VP, VP, VP]),
+    "rc_resample_mantel": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_uint64, VP, ctypes.c_int32, VP, VP,
+                                          ctypes.c_int32, ctypes.c_int32, VP, VP, VP, VP, VP, VP]),
     "rc_timings": (ctypes.c_int, [VP, P(RcTiming)]),
     "rc_dust_mask": (ctypes.c_int, [VP, ctypes.c_int32, VP, ctypes.c_uint64, P(ctypes.c_uint64)]),
     "rc_dust_masks": (ctypes.c_int, [VP, VP, ctypes.c_int32, VP, ctypes.c_uint64, P(ctypes.c_uint64), ctypes.c_int]),

@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librcgpu.so")
-SOURCES = ["kernels.hip", "components.hip", "nj.hip", "splits.hip", "pcoa.hip", "groups.hip", "sort.hip", "seed.hip", "align.hip", "rows.hip",
+SOURCES = ["kernels.hip", "components.hip", "nj.hip", "splits.hip", "pcoa.hip", "groups.hip", "dispersion.hip", "mantel.hip", "sort.hip", "seed.hip", "align.hip", "rows.hip",
            "finish.hip", "extend.hip", "group.hip", "dust.hip",
            "engine.hip", "results.hip", "analysis.hip", "fasta.cpp", "graph_pickle.cpp", "od2_tables.cpp"]
 HEADERS = ["device.h", "launch.h", "align_common.h", "engine.h", "fail.h", "graph_pickle.h",

@@ -1,7 +1,8 @@
 // Analyses of a finished engine's graph: per-component tables, bootstrap
 // resampling, neighbour-joining trees, the census of their splits, principal
-// coordinates and group tests (kernels: components.hip, nj.hip, splits.hip,
-// pcoa.hip, groups.hip).
+// coordinates, group tests, PERMDISP and the Mantel test (kernels:
+// components.hip, nj.hip, splits.hip, pcoa.hip, groups.hip, dispersion.hip,
+// mantel.hip).
 #include "engine.h"
 
 // ------------------------------------------------------------------------
@@ -678,11 +679,13 @@ int rc_resample_pcoa(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint6
 
 static const int GROUP_MAX_SAMPLES = 128;
 
-// The argument checks of rc_group_test / rc_resample_group_test (no device
-// work). lab8: the observed labels, then the n_perm permuted rows, one byte
+// The argument checks of rc_group_test / rc_resample_group_test and of
+// rc_group_dispersion / rc_resample_group_dispersion (no device work; chunk:
+// the permutations one workgroup of the test's kernel walks). lab8: the observed labels, then the n_perm permuted rows, one byte
 // each; *m_within: the within-group pairs.
 static int group_check(int32_t n_rep, int32_t n, const int32_t *labels, int32_t a, const int32_t *perm, int32_t n_perm,
-                       int32_t method, std::vector<uint8_t> &lab8, uint32_t *m_within)
+                       int32_t method, std::vector<uint8_t> &lab8, uint32_t *m_within,
+                       uint64_t chunk = GROUP_PERM_CHUNK)
 {
     if (n > GROUP_MAX_SAMPLES) return fail(RC_E_LIMIT, "more than 128 samples in a group test");
     if (!labels || (n_perm > 0 && !perm)) return fail(RC_E_ARG, "null argument");
@@ -690,7 +693,7 @@ static int group_check(int32_t n_rep, int32_t n, const int32_t *labels, int32_t 
     if (n_perm < 0) return fail(RC_E_ARG, "n_perm must be >= 0");
     if (method != RC_GROUP_PERMANOVA && method != RC_GROUP_ANOSIM) return fail(RC_E_ARG, "unknown group test");
     if (a < 2 || a >= n) return fail(RC_E_ARG, "a group test needs 2 <= n_groups < n");
-    if (((uint64_t)n_perm + GROUP_PERM_CHUNK - 1) / GROUP_PERM_CHUNK * (uint64_t)n_rep >> 31)
+    if (((uint64_t)n_perm + chunk - 1) / chunk * (uint64_t)n_rep >> 31)
         return fail(RC_E_LIMIT, "n_rep x permutations beyond the group test's grid");
     std::vector<int32_t> size(a, 0), seen(a);
     lab8.resize(((size_t)n_perm + 1) * n);
@@ -806,6 +809,244 @@ int rc_resample_group_test(rc_engine *e, const uint16_t *weights, int32_t n_rep,
     CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
     CHK(group_device(e, e->d_dist.p, n_rep, n, n_groups, mw, lab8, n_perm, method, stat, n_ge, total, within, perm_stat,
                      valid, &invalid));
+    e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
+    if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    return RC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// PERMDISP (dispersion.hip)
+// ------------------------------------------------------------------------
+
+// PERMDISP of the n_rep matrices at dD (device, n x n each); the arguments have
+// passed group_check. Events EV_DISP0, EV_DISP1. *invalid: the number of
+// matrices with a non-finite entry.
+static int dispersion_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, int32_t a,
+                             const std::vector<uint8_t> &lab8, int32_t n_perm, double *stat, uint32_t *n_ge,
+                             double *total, double *within, double *perm_stat, double *dist, uint8_t *valid,
+                             uint32_t *invalid)
+{
+    rc_engine::Analysis &an = e->an;
+    const size_t R = (size_t)n_rep, np = perm_stat ? R * (size_t)n_perm : 0, nz = R * (size_t)n;
+    int lds_max = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
+    if (dispersion_lds_bytes(n) + 4096 > (size_t)lds_max)
+        return fail(RC_E_LIMIT, "this device's LDS does not hold a matrix of " + std::to_string(n) + " samples");
+    CHK(an.d_gt_labels.ensure(lab8.size()));
+    CHK(an.d_gt_stat.ensure(R));
+    CHK(an.d_gt_total.ensure(R));
+    CHK(an.d_gt_within.ensure(R));
+    CHK(an.d_gt_nge.ensure(R));
+    CHK(an.d_gt_valid.ensure(R));
+    CHK(an.d_gt_dist.ensure(nz));
+    if (np) CHK(an.d_gt_perm.ensure(np));
+    HIPCHK(hipMemcpyAsync(an.d_gt_labels.p, lab8.data(), lab8.size(), hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemsetAsync(an.d_gt_nge.p, 0, R * 4, e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_DISP0], e->st));
+    const hipError_t err =
+        launch_dispersion(dD, n_rep, n, a, an.d_gt_labels.p, an.d_gt_labels.p + n, n_perm, an.d_gt_stat.p, an.d_gt_nge.p,
+                          an.d_gt_total.p, an.d_gt_within.p, np ? an.d_gt_perm.p : nullptr, an.d_gt_dist.p,
+                          an.d_gt_valid.p, e->st);
+    if (err != hipSuccess)
+        return fail(RC_E_HIP, std::string("dispersion_kernel (") + std::to_string(dispersion_lds_bytes(n)) +
+                                  " bytes of LDS): " + hipGetErrorString(err));
+    HIPCHK(hipEventRecord(e->ev[EV_DISP1], e->st));
+    std::vector<uint8_t> hv(R);
+    if (stat) HIPCHK(hipMemcpyAsync(stat, an.d_gt_stat.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (n_ge) HIPCHK(hipMemcpyAsync(n_ge, an.d_gt_nge.p, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (total) HIPCHK(hipMemcpyAsync(total, an.d_gt_total.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (within) HIPCHK(hipMemcpyAsync(within, an.d_gt_within.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (np) HIPCHK(hipMemcpyAsync(perm_stat, an.d_gt_perm.p, np * 8, hipMemcpyDeviceToHost, e->st));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, an.d_gt_dist.p, nz * 8, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(hv.data(), an.d_gt_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.disp_ms = ev_ms(e, EV_DISP0, EV_DISP1);
+    uint32_t bad = 0;
+    for (size_t r = 0; r < R; r++) bad += !hv[r];
+    if (valid) std::copy(hv.begin(), hv.end(), valid);
+    *invalid = bad;
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_group_dispersion(rc_engine *e, const double *D, int32_t n_rep, int32_t n, const int32_t *labels,
+                        int32_t n_groups, const int32_t *perm_labels, int32_t n_perm, double *stat, uint32_t *n_ge,
+                        double *total, double *within, double *perm_stat, double *dist, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    std::vector<uint8_t> lab8;
+    uint32_t mw = 0, invalid = 0;
+    CHK(group_check(n_rep, n, labels, n_groups, perm_labels, n_perm, RC_GROUP_PERMANOVA, lab8, &mw, DISP_PERM_CHUNK));
+    if (!D) return fail(RC_E_ARG, "null argument");
+    CHK(set_device(e));
+    const size_t nd = (size_t)n_rep * n * n;
+    CHK(e->an.d_gt_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->an.d_gt_in.p, D, nd * 8, hipMemcpyHostToDevice, e->st));
+    CHK(dispersion_device(e, e->an.d_gt_in.p, n_rep, n, n_groups, lab8, n_perm, stat, n_ge, total, within, perm_stat,
+                          dist, valid, &invalid));
+    if (invalid) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no dispersion test for it");
+    return RC_OK;
+}
+
+int rc_resample_group_dispersion(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp,
+                                 const int32_t *order, int32_t n, const int32_t *labels, int32_t n_groups,
+                                 const int32_t *perm_labels, int32_t n_perm, double *stat, uint32_t *n_ge,
+                                 double *total, double *within, double *perm_stat, double *dist, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    std::vector<uint8_t> lab8;
+    uint32_t mw = 0, invalid = 0;
+    CHK(group_check(n_rep, n, labels, n_groups, perm_labels, n_perm, RC_GROUP_PERMANOVA, lab8, &mw, DISP_PERM_CHUNK));
+    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
+    CHK(dispersion_device(e, e->d_dist.p, n_rep, n, n_groups, lab8, n_perm, stat, n_ge, total, within, perm_stat, dist,
+                          valid, &invalid));
+    e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
+    if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
+    return RC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------
+// the Mantel test (mantel.hip)
+// ------------------------------------------------------------------------
+
+static const int MANTEL_MAX_SAMPLES = 128;
+
+// The argument checks of rc_mantel / rc_resample_mantel (no device work).
+// perm8: the permutations, one byte per position.
+static int mantel_check(int32_t n_rep, int32_t n, const double *Y, const int32_t *perms, int32_t n_perm, int32_t method,
+                        std::vector<uint8_t> &perm8)
+{
+    if (n > MANTEL_MAX_SAMPLES) return fail(RC_E_LIMIT, "more than 128 samples in a Mantel test");
+    if (!Y || (n_perm > 0 && !perms)) return fail(RC_E_ARG, "null argument");
+    if (n < 3) return fail(RC_E_ARG, "a Mantel test needs at least 3 samples");
+    if (n_rep < 1) return fail(RC_E_ARG, "n_rep must be >= 1");
+    if (n_perm < 0) return fail(RC_E_ARG, "n_perm must be >= 0");
+    if (method != RC_MANTEL_PEARSON && method != RC_MANTEL_SPEARMAN) return fail(RC_E_ARG, "unknown Mantel method");
+    if (((uint64_t)n_perm + MANTEL_PERM_CHUNK - 1) / MANTEL_PERM_CHUNK * (uint64_t)n_rep >> 31)
+        return fail(RC_E_LIMIT, "n_rep x permutations beyond the Mantel test's grid");
+    for (int i = 0; i < n; i++)
+        for (int j = i + 1; j < n; j++)
+            if (!std::isfinite(Y[(size_t)i * n + j])) return fail(RC_E_ARG, "a non-finite entry above Y's diagonal");
+    perm8.resize((size_t)n_perm * n);
+    std::vector<uint8_t> seen(n);
+    for (int64_t p = 0; p < n_perm; p++) {
+        const int32_t *row = perms + p * n;
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int i = 0; i < n; i++) {
+            if (row[i] < 0 || row[i] >= n || seen[row[i]]++)
+                return fail(RC_E_ARG, "a row of perms is not a rearrangement of 0..n-1");
+            perm8[(size_t)p * n + i] = (uint8_t)row[i];
+        }
+    }
+    return RC_OK;
+}
+
+// The Mantel test of the n_rep matrices at dD (device, n x n each) against Y
+// (host, n x n); the arguments have passed mantel_check. Events EV_MANTEL0,
+// EV_MANTEL1. *invalid: the number of matrices with a non-finite entry.
+static int mantel_device(rc_engine *e, const double *dD, int32_t n_rep, int32_t n, const double *Y,
+                         const std::vector<uint8_t> &perm8, int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge,
+                         uint32_t *n_le, uint32_t *n_abs_ge, double *perm_stat, uint8_t *valid, uint32_t *invalid)
+{
+    rc_engine::Analysis &an = e->an;
+    const size_t R = (size_t)n_rep, np = perm_stat ? R * (size_t)n_perm : 0, nn = (size_t)n * n;
+    const bool spearman = method == RC_MANTEL_SPEARMAN;
+    int lds_max = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->o.device));
+    if (std::max(mantel_lds_bytes(method, n), spearman ? group_rank_lds_bytes(n) : 0) + 4096 > (size_t)lds_max)
+        return fail(RC_E_LIMIT, "this device's LDS does not hold a matrix of " + std::to_string(n) + " samples");
+    CHK(an.d_mt_perms.ensure(perm8.size() + 1));
+    CHK(an.d_mt_y.ensure(nn));
+    CHK(an.d_mt_stat.ensure(R));
+    CHK(an.d_mt_counts.ensure(3 * R));
+    CHK(an.d_mt_valid.ensure(R));
+    if (np) CHK(an.d_mt_perm.ensure(np));
+    if (spearman) {
+        CHK(an.d_mt_rank.ensure(R * nn));
+        CHK(an.d_mt_yrank.ensure(nn));
+        CHK(an.d_mt_yvalid.ensure(1));
+    }
+    std::vector<double> yc(nn);
+    double syy = 0.0;
+    int y_const = 0;
+    if (spearman)
+        std::copy(Y, Y + nn, yc.begin());
+    else
+        mantel_prepare_y(Y, n, yc.data(), &syy, &y_const);
+    HIPCHK(hipMemcpyAsync(an.d_mt_y.p, yc.data(), nn * 8, hipMemcpyHostToDevice, e->st));
+    if (!perm8.empty())
+        HIPCHK(hipMemcpyAsync(an.d_mt_perms.p, perm8.data(), perm8.size(), hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemsetAsync(an.d_mt_counts.p, 0, 3 * R * 4, e->st));
+    HIPCHK(hipEventRecord(e->ev[EV_MANTEL0], e->st));
+    if (spearman) {
+        hipError_t err = launch_group_rank(dD, n_rep, n, an.d_mt_rank.p, an.d_mt_valid.p, e->st);
+        if (err == hipSuccess) err = launch_group_rank(an.d_mt_y.p, 1, n, an.d_mt_yrank.p, an.d_mt_yvalid.p, e->st);
+        if (err != hipSuccess)
+            return fail(RC_E_HIP, std::string("group_rank_kernel (") + std::to_string(group_rank_lds_bytes(n)) +
+                                      " bytes of LDS): " + hipGetErrorString(err));
+    }
+    const hipError_t err = launch_mantel(
+        method, spearman ? (const void *)an.d_mt_rank.p : (const void *)dD, an.d_mt_valid.p, n_rep, n,
+        spearman ? (const void *)an.d_mt_yrank.p : (const void *)an.d_mt_y.p, syy, y_const, an.d_mt_perms.p, n_perm,
+        an.d_mt_stat.p, an.d_mt_counts.p, an.d_mt_counts.p + R, an.d_mt_counts.p + 2 * R,
+        np ? an.d_mt_perm.p : nullptr, an.d_mt_valid.p, e->st);
+    if (err != hipSuccess)
+        return fail(RC_E_HIP, std::string("mantel_kernel (") + std::to_string(mantel_lds_bytes(method, n)) +
+                                  " bytes of LDS): " + hipGetErrorString(err));
+    HIPCHK(hipEventRecord(e->ev[EV_MANTEL1], e->st));
+    std::vector<uint8_t> hv(R);
+    if (stat) HIPCHK(hipMemcpyAsync(stat, an.d_mt_stat.p, R * 8, hipMemcpyDeviceToHost, e->st));
+    if (n_ge) HIPCHK(hipMemcpyAsync(n_ge, an.d_mt_counts.p, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (n_le) HIPCHK(hipMemcpyAsync(n_le, an.d_mt_counts.p + R, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (n_abs_ge) HIPCHK(hipMemcpyAsync(n_abs_ge, an.d_mt_counts.p + 2 * R, R * 4, hipMemcpyDeviceToHost, e->st));
+    if (np) HIPCHK(hipMemcpyAsync(perm_stat, an.d_mt_perm.p, np * 8, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipMemcpyAsync(hv.data(), an.d_mt_valid.p, R, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->tm.mantel_ms = ev_ms(e, EV_MANTEL0, EV_MANTEL1);
+    uint32_t bad = 0;
+    for (size_t r = 0; r < R; r++) bad += !hv[r];
+    if (valid) std::copy(hv.begin(), hv.end(), valid);
+    *invalid = bad;
+    return RC_OK;
+}
+
+extern "C" {
+
+int rc_mantel(rc_engine *e, const double *X, int32_t n_rep, int32_t n, const double *Y, const int32_t *perms,
+              int32_t n_perm, int32_t method, double *stat, uint32_t *n_ge, uint32_t *n_le, uint32_t *n_abs_ge,
+              double *perm_stat, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    std::vector<uint8_t> perm8;
+    uint32_t invalid = 0;
+    CHK(mantel_check(n_rep, n, Y, perms, n_perm, method, perm8));
+    if (!X) return fail(RC_E_ARG, "null argument");
+    CHK(set_device(e));
+    const size_t nd = (size_t)n_rep * n * n;
+    CHK(e->an.d_mt_in.ensure(nd));
+    HIPCHK(hipMemcpyAsync(e->an.d_mt_in.p, X, nd * 8, hipMemcpyHostToDevice, e->st));
+    CHK(mantel_device(e, e->an.d_mt_in.p, n_rep, n, Y, perm8, n_perm, method, stat, n_ge, n_le, n_abs_ge, perm_stat,
+                      valid, &invalid));
+    if (invalid) return fail(RC_E_NO_IDEAL, "a distance matrix has a non-finite entry: no Mantel test for it");
+    return RC_OK;
+}
+
+int rc_resample_mantel(rc_engine *e, const uint16_t *weights, int32_t n_rep, uint64_t n_comp, const int32_t *order,
+                       int32_t n, const double *Y, const int32_t *perms, int32_t n_perm, int32_t method, double *stat,
+                       uint32_t *n_ge, uint32_t *n_le, uint32_t *n_abs_ge, double *perm_stat, uint8_t *valid)
+{
+    if (!e) return fail(RC_E_ARG, "null argument");
+    std::vector<uint8_t> perm8;
+    uint32_t invalid = 0;
+    CHK(mantel_check(n_rep, n, Y, perms, n_perm, method, perm8));
+    CHK(resample_fill(e, weights, n_rep, n_comp, order, n, true, true));
+    CHK(mantel_device(e, e->d_dist.p, n_rep, n, Y, perm8, n_perm, method, stat, n_ge, n_le, n_abs_ge, perm_stat, valid,
+                      &invalid));
     e->tm.resample_ms = ev_ms(e, EV_RESAMPLE0, EV_RESAMPLE1);
     if (invalid) return fail(RC_E_NO_IDEAL, "No ideal components found. Cannot report distances!");
     return RC_OK;

@@ -190,6 +190,8 @@ enum Ev {
     EV_PCOA0 = 16, EV_PCOA1 = 17,           // pcoa_device: the ordinations (pcoa_ms)
     EV_SPLIT0 = 18, EV_SPLIT1 = 19,         // rc_split_census, rc_tree_rf: the census and RF kernels (split_ms)
     EV_GROUP0 = 20, EV_GROUP1 = 21,         // group_device: the ranking and test kernels (group_ms)
+    EV_DISP0 = 22, EV_DISP1 = 23,           // dispersion_device: the PERMDISP kernel (disp_ms)
+    EV_MANTEL0 = 24, EV_MANTEL1 = 25,       // mantel_device: the ranking and Mantel kernels (mantel_ms)
     EV_N
 };
 // rc_engine::evd: DUST on the second stream
@@ -418,6 +420,14 @@ struct rc_engine {
         DBuf<double> d_gt_in, d_gt_stat, d_gt_total, d_gt_within, d_gt_perm;
         DBuf<uint8_t> d_gt_labels, d_gt_valid;
         DBuf<uint32_t> d_gt_rank, d_gt_nge;
+        // PERMDISP (dispersion.hip) shares the group tests' buffers; the observed distances to the centroids
+        DBuf<double> d_gt_dist;
+        // the Mantel test (mantel.hip): input matrices of rc_mantel, Y as the kernel reads it (centred doubles
+        // or twice-ranks) with its raw upload and validity, the permutations (one byte each), X's twice-ranks
+        // and the results (counts: >=, <=, |.| >= |.|, n_rep each)
+        DBuf<double> d_mt_in, d_mt_y, d_mt_stat, d_mt_perm;
+        DBuf<uint8_t> d_mt_perms, d_mt_valid, d_mt_yvalid;
+        DBuf<uint32_t> d_mt_rank, d_mt_yrank, d_mt_counts;
     };
     Analysis an;
 

@@ -1,5 +1,5 @@
 // The host entry points of the kernel files: every non-static host function
-// that kernels.hip, components.hip, nj.hip, splits.hip, pcoa.hip, groups.hip, sort.hip,
+// that kernels.hip, components.hip, nj.hip, splits.hip, pcoa.hip, groups.hip, dispersion.hip, mantel.hip, sort.hip,
 // seed.hip, align.hip, rows.hip, finish.hip, extend.hip, group.hip and dust.hip define,
 // one section per unit, declared here and nowhere else. The defining files
 // include this header too, so a definition whose return type drifts from its
@@ -87,6 +87,18 @@ hipError_t launch_group_rank(const double *, int, int, uint32_t *, uint8_t *, hi
 hipError_t launch_group_test(int, const void *, const uint8_t *, int, int, int, uint32_t, const uint8_t *,
                              const uint8_t *, int, double *, uint32_t *, double *, double *, double *, uint8_t *,
                              hipStream_t);
+// dispersion.hip
+enum { DISP_PERM_CHUNK = 124 };                   // permutations per workgroup
+size_t dispersion_lds_bytes(int);
+hipError_t launch_dispersion(const double *, int, int, int, const uint8_t *, const uint8_t *, int, double *, uint32_t *,
+                             double *, double *, double *, double *, uint8_t *, hipStream_t);
+// mantel.hip
+enum { MANTEL_PEARSON = 0, MANTEL_SPEARMAN = 1 };   // rcgpu.h: RC_MANTEL_PEARSON, RC_MANTEL_SPEARMAN
+enum { MANTEL_PERM_CHUNK = 124 };                   // permutations per workgroup
+size_t mantel_lds_bytes(int, int);
+void mantel_prepare_y(const double *, int, double *, double *, int *);
+hipError_t launch_mantel(int, const void *, const uint8_t *, int, int, const void *, double, int, const uint8_t *, int,
+                         double *, uint32_t *, uint32_t *, uint32_t *, double *, uint8_t *, hipStream_t);
 // sort.hip
 uint64_t os_status_words(uint64_t n);
 uint64_t os_scratch_words(uint64_t n);

@@ -609,6 +609,119 @@ class Engine:
             nat.check(code)
         return [self.labels[i] for i in order], self._group_result(method, m, n_groups, perms, bufs)
 
+    # ------------------------------------------------------------ PERMDISP
+    @classmethod
+    def _dispersion_args(cls, r, m, labels, perm_labels, perm_stats):
+        """_group_args for rc_group_dispersion: no method, and the observed
+        distances (r, m) before `valid`."""
+        (lab, perms), _, bufs, tail = cls._group_args(r, m, labels, perm_labels, "permanova", perm_stats)
+        bufs["dist"] = np.zeros((r, m), dtype=np.float64)
+        tail = (*tail[:4], *tail[5:10], bufs["dist"].ctypes.data_as(ctypes.c_void_p), tail[10])
+        return lab, perms, bufs, tail
+
+    @staticmethod
+    def _dispersion_result(lab, perms, bufs):
+        from .groups import DispersionResult
+        return DispersionResult.from_counts(lab, len(perms), bufs["stat"], bufs["n_ge"], bufs["total"], bufs["within"],
+                                            bufs["dist"], bufs["valid"], bufs["perm_stat"])
+
+    def group_dispersion(self, matrices, labels, perm_labels=None, *, perm_stats=False, allow_nan=False):
+        """PERMDISP (centroid form) of distance matrices (R, N, N) or (N, N):
+        do the groups spread equally about their centroids? (rc_group_dispersion;
+        the engine may be in any state; N <= 128, else groups.dispersion_host).
+        labels, perm_labels, allow_nan and the errors as group_test(). Returns
+        groups.DispersionResult with one entry per matrix."""
+        d = self._matrices(matrices)
+        r, m = d.shape[0], d.shape[1]
+        lab, perms, bufs, tail = self._dispersion_args(r, m, labels, perm_labels, perm_stats)
+        code = nat.lib().rc_group_dispersion(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, *tail)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return self._dispersion_result(lab, perms, bufs)
+
+    def resample_group_dispersion(self, weights, labels, perm_labels=None, order=None, *, perm_stats=False,
+                                  allow_nan=False):
+        """PERMDISP of every replicate of resample(weights, order): the
+        matrices stay on the device (rc_resample_group_dispersion). Arguments
+        as resample_group_test(). Returns (labels of the samples,
+        DispersionResult)."""
+        w, order = self._weights(weights), self._order(order)
+        m, r = len(order), w.shape[0]
+        lab, perms, bufs, tail = self._dispersion_args(r, m, labels, perm_labels, perm_stats)
+        vp = ctypes.c_void_p
+        code = nat.lib().rc_resample_group_dispersion(self._h, w.ctypes.data_as(vp), r, w.shape[1],
+                                                      order.ctypes.data_as(vp), m, *tail)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return [self.labels[i] for i in order], self._dispersion_result(lab, perms, bufs)
+
+    # ------------------------------------------------------- the Mantel test
+    @staticmethod
+    def _mantel_args(r, m, other, perms, method, perm_stats):
+        """Y and the permutations as the library reads them (it checks them),
+        the output buffers and the tail of rc_mantel's arguments."""
+        from .mantel import method_code
+        code = method_code(method)
+        y = np.ascontiguousarray(other, dtype=np.float64)
+        if y.shape != (m, m):
+            raise ValueError("Y must be a square matrix of the samples of X")
+        pm = np.zeros((0, m), dtype=np.int32) if perms is None else np.ascontiguousarray(perms, dtype=np.int32)
+        if pm.size == 0:
+            pm = pm.reshape(0, m)
+        if pm.ndim != 2 or pm.shape[1] != m:
+            raise ValueError("perms must have shape (permutations, N)")
+        p = len(pm)
+        bufs = {"stat": np.zeros(r, dtype=np.float64), "n_ge": np.zeros(r, dtype=np.uint32),
+                "n_le": np.zeros(r, dtype=np.uint32), "n_abs_ge": np.zeros(r, dtype=np.uint32),
+                "perm_stat": np.zeros((r, p), dtype=np.float64) if perm_stats else None,
+                "valid": np.zeros(r, dtype=np.uint8)}
+        vp = ctypes.c_void_p
+        ptr = lambda a: None if a is None else a.ctypes.data_as(vp)   # noqa: E731
+        tail = (ptr(y), ptr(pm) if p else None, p, code, *(ptr(a) for a in bufs.values()))
+        return (y, pm), bufs, tail
+
+    @staticmethod
+    def _mantel_result(method, m, pm, bufs):
+        from .mantel import MantelResult
+        return MantelResult.from_counts(method, m, len(pm), bufs["stat"], bufs["n_ge"], bufs["n_le"], bufs["n_abs_ge"],
+                                        bufs["valid"], bufs["perm_stat"])
+
+    def mantel(self, matrices, other, perms=None, method="pearson", *, perm_stats=False, allow_nan=False):
+        """The Mantel test of distance matrices X (R, N, N) or (N, N) against
+        one matrix `other` (N, N): the correlation ("pearson" or "spearman")
+        of the entries above the diagonal, and how many of the permutations
+        perms (P, N; mantel.permutations) of X's rows and columns reach it
+        (rc_mantel; the engine may be in any state; 3 <= N <= 128, else
+        mantel.mantel_host). Returns mantel.MantelResult with one entry per
+        matrix. Raises NativeError(RC_E_NO_IDEAL) when a matrix of X has a
+        non-finite entry, unless allow_nan (that replicate is then NaN and
+        flagged in `valid`)."""
+        d = self._matrices(matrices)
+        r, m = d.shape[0], d.shape[1]
+        (y, pm), bufs, tail = self._mantel_args(r, m, other, perms, method, perm_stats)
+        code = nat.lib().rc_mantel(self._h, d.ctypes.data_as(ctypes.c_void_p), r, m, *tail)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return self._mantel_result(method, m, pm, bufs)
+
+    def resample_mantel(self, weights, other, perms=None, order=None, method="pearson", *, perm_stats=False,
+                        allow_nan=False):
+        """The Mantel test of every replicate of resample(weights, order)
+        against `other`, whose rows and columns stand for the samples of
+        `order`: the replicate matrices stay on the device
+        (rc_resample_mantel). Returns (labels of the samples, MantelResult).
+        Errors as mantel(); RC_E_NO_IDEAL: a replicate has a pair without
+        rows."""
+        w, order = self._weights(weights), self._order(order)
+        m, r = len(order), w.shape[0]
+        (y, pm), bufs, tail = self._mantel_args(r, m, other, perms, method, perm_stats)
+        vp = ctypes.c_void_p
+        code = nat.lib().rc_resample_mantel(self._h, w.ctypes.data_as(vp), r, w.shape[1], order.ctypes.data_as(vp), m,
+                                            *tail)
+        if not (allow_nan and code == nat.RC_E_NO_IDEAL):
+            nat.check(code)
+        return [self.labels[i] for i in order], self._mantel_result(method, m, pm, bufs)
+
     def dust_mask(self, s):
         """DUST mask of sample s (uint8 per base, 1 = masked query base)."""
         return self._sized(nat.lib().rc_dust_mask, np.uint8, int(s))

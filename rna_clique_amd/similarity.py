@@ -642,6 +642,116 @@ class SampleSimilarity:
                                                              samples=sub)
         return out
 
+    # --------------------------------------------------------- PERMDISP
+    def resampled_permdisp(self, weights, grouping, permutations=999, seed=0, *, perm_stats=False, samples=None):
+        """PERMDISP (groups.DispersionResult, one entry per row of `weights`)
+        of resampled_dissimilarity_matrices(weights); arguments as
+        resampled_group_test. On the GPU without the matrices leaving it; with
+        more than 128 samples, groups.dispersion_host on the matrices."""
+        from .groups import MAX_GPU_SAMPLES, dispersion_host, encode_grouping, permuted_labels
+        names = self.samples if samples is None else samples
+        if len(names) > MAX_GPU_SAMPLES:
+            labels, groups_ = encode_grouping(names, grouping)
+            if not 2 <= len(groups_) < len(names):
+                raise ValueError("a group test needs at least 2 groups and fewer groups than samples")
+            index = {s: i for i, s in enumerate(self.samples)}
+            keep = [index[s] for s in names]
+            mats = self.resampled_dissimilarity_matrices(weights)[:, keep][:, :, keep]
+            return dispersion_host(mats, labels, permuted_labels(labels, permutations, seed), perm_stats=perm_stats)
+        order, labels, _, perms = self._group_design(grouping, permutations, seed, samples)
+        try:
+            return self.engine.resample_group_dispersion(weights, labels, perms, order, perm_stats=perm_stats)[1]
+        except nat.NativeError as e:
+            if e.code == nat.RC_E_NO_IDEAL:
+                raise NoIdealComponentsError() from e
+            raise
+
+    def permdisp(self, grouping, permutations=999, seed=0, *, samples=None):
+        """PERMDISP (Anderson 2006, centroid form) of get_dissimilarity_matrix()
+        for the groups of `grouping`: do the groups spread equally about their
+        centroids? What skbio.stats.distance.permdisp(test="centroid") answers;
+        read it beside permanova(), which cannot tell a difference in location
+        from one in spread. Returns groups.DispersionResult with scalar fields:
+        statistic (F), p_value, distances (one per sample), group_means."""
+        c = self.engine.n_components()
+        if c == 0:
+            raise NoIdealComponentsError()
+        return self.resampled_permdisp(np.ones((1, c), dtype=np.uint16), grouping, permutations, seed,
+                                       samples=samples).first()
+
+    def bootstrap_permdisp(self, grouping, n_rep, seed=0, permutations=999):
+        """(permdisp of the full matrix, permdisp of each of n_rep bootstrap
+        replicates over the ideal components), as bootstrap_group_test."""
+        ref = self.permdisp(grouping, permutations, seed)
+        w = bootstrap_weights(self.engine.n_components(), n_rep, seed)
+        return ref, self.resampled_permdisp(w, grouping, permutations, seed)
+
+    def pairwise_permdisp(self, grouping, permutations=999, seed=0) -> dict:
+        """One PERMDISP per pair of groups, on the sub-matrix of the two
+        groups' samples, as pairwise_group_tests: {(group, other group):
+        DispersionResult}, p-values uncorrected; a pair of two single samples
+        is left out."""
+        from .groups import encode_grouping
+        labels, names = encode_grouping(self.samples, grouping)
+        which = {s: names[g] for s, g in zip(self.samples, labels)}
+        out = {}
+        for i in range(len(names)):
+            for j in range(i + 1, len(names)):
+                sub = [s for s, g in zip(self.samples, labels) if g in (i, j)]
+                if len(sub) >= 3:
+                    out[(names[i], names[j])] = self.permdisp({s: which[s] for s in sub}, permutations, seed,
+                                                              samples=sub)
+        return out
+
+    # ----------------------------------------------------- the Mantel test
+    def resampled_mantel(self, weights, other, method="pearson", permutations=999, seed=0, *, strict=True,
+                         perm_stats=False):
+        """The Mantel test (mantel.MantelResult, one entry per row of
+        `weights`) of resampled_dissimilarity_matrices(weights) against
+        `other`: a DataFrame with sample labels on both axes, or a (labels,
+        matrix) pair -- geography, another method's distances,
+        UnfilteredSimilarity.get_dissimilarity_df(). It is aligned by sample
+        label; samples missing on either side raise ValueError unless strict
+        is False, which tests the common ones (scikit-bio's rule). The
+        permutations are mantel.permutations(samples, permutations, seed), the
+        same rows for every replicate. On the GPU without the matrices leaving
+        it; with more than 128 samples, mantel.mantel_host on the matrices."""
+        from .mantel import MAX_GPU_SAMPLES, align_matrix, mantel_host
+        from .mantel import permutations as draw
+        common, pos, y = align_matrix(self.samples, other, strict)
+        perms = draw(len(common), permutations, seed)
+        if len(common) > MAX_GPU_SAMPLES:
+            mats = self.resampled_dissimilarity_matrices(weights)[:, pos][:, :, pos]
+            return mantel_host(mats, y, perms, method, perm_stats=perm_stats)
+        o = self._order()
+        try:
+            return self.engine.resample_mantel(weights, y, perms, [o[i] for i in pos], method,
+                                               perm_stats=perm_stats)[1]
+        except nat.NativeError as e:
+            if e.code == nat.RC_E_NO_IDEAL:
+                raise NoIdealComponentsError() from e
+            raise
+
+    def mantel(self, other, method="pearson", permutations=999, seed=0, *, strict=True):
+        """The Mantel test of get_dissimilarity_matrix() against `other` (as
+        resampled_mantel takes it): do the two sets of distances agree? What
+        skbio.stats.distance.mantel answers. Returns mantel.MantelResult with
+        scalar fields: statistic (r), p_value(alternative), n, permutations."""
+        c = self.engine.n_components()
+        if c == 0:
+            raise NoIdealComponentsError()
+        return self.resampled_mantel(np.ones((1, c), dtype=np.uint16), other, method, permutations, seed,
+                                     strict=strict).first()
+
+    def bootstrap_mantel(self, other, n_rep, seed=0, method="pearson", permutations=999, *, strict=True):
+        """(the test of the full matrix, the test of each of n_rep bootstrap
+        replicates over the ideal components): how stable the agreement with
+        `other` is under resampling. Both use the same permutations; the
+        replicate matrices never leave the device."""
+        ref = self.mantel(other, method, permutations, seed, strict=strict)
+        w = bootstrap_weights(self.engine.n_components(), n_rep, seed)
+        return ref, self.resampled_mantel(w, other, method, permutations, seed, strict=strict)
+
 
 def _table_sums(df: pd.DataFrame):
     """(sum nident, sum length - sum gaps) of one gene matches table, as exact
